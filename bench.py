@@ -2,8 +2,18 @@
 """bench.py -- GCUPS of the MI355X affine-gap aligner on synthetic 30k x 30k
 DNA pairs (BASELINE.json metric), 1..8 GPUs, one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs-per-gpu P]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--pairs-per-gpu P] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run stages the inputs, warms up, times the K steps and prints the
+result line (headline GCUPS, ms_per_step, the roofline of the timed fill from
+the committed profiles).  --full adds everything else to the line: the parity
+checks against the oracle digests (timed passes and extra passes with plane
+checksums), the same batch with byte / int32 / no planes, the single pair,
+BASELINE configs 2 and 3, the local batch and the CPU baselines.
+--dump-outputs DIR writes what the last timed step returned to its caller
+(per-pair results and labelled alignments) as DIR/<name>.npy; the inputs are
+seeded, so two builds can be compared output for output.
 
 A STEP is one pass of the hot path over one batch: for each of the P
 synthetic 30k x 30k pairs resident on this GPU, the full-table fill that
@@ -24,10 +34,11 @@ with compact planes, 20 with int32 planes).
 roofline: the fill kernel's score-plane writes, B bytes per cell (3 compact,
 12 int32); achieved = B * cells / average fill-kernel time
 from HIP events on the kernel's own stream.  With compact planes the fill is
-issue-bound rather than HBM-bound: no_plane_fill times the same batch without
-plane stores (the kernel's compute ceiling) for comparison.  cpu_baseline: the reference-layout C
-restatement (oracle/, 48-B cells, column-major, i-outer/j-inner, one core)
-on the first R rows of the same synthetic pair.
+issue-bound rather than HBM-bound: with --full, no_plane_fill times the same
+batch without plane stores (the kernel's compute ceiling) for comparison.
+cpu_baseline (--full): the reference-layout C restatement (oracle/, 48-B
+cells, column-major, i-outer/j-inner, one core) on the first R rows of the
+same synthetic pair.
 """
 import argparse
 import json
@@ -542,6 +553,54 @@ def alignment_sha256(steps) -> str:
     return h.hexdigest()
 
 
+DUMP_RESULT_FIELDS = ("score", "matches", "mismatches", "gap_extensions", "opening_gaps", "n_steps",
+                      "start_i", "start_j")
+DUMP_ALIGNMENT_BYTES = 48 << 20   # of the 64 MB a dump may take; the per-pair results are a few KB
+
+
+def dump_outputs(path: str, staged, res, rank: int, world: int):
+    """--dump-outputs: what the last timed step handed its caller, as float
+    .npy files under `path` (call before anything else runs on `staged`):
+      results.npy              float64 [pairs, 8]: DUMP_RESULT_FIELDS of every pair
+      alignment.npy            [steps, 3]: (choice, i, j) of the labelled alignments of the
+                               sampled pairs, one after another (float32: exact below 2^24,
+                               else float64)
+      alignment_pairs.npy      float64 [k]: the sampled pairs' indices
+      alignment_offsets.npy    float64 [k + 1]: pair alignment_pairs[x] owns rows offsets[x]:offsets[x + 1]
+    The sample is all pairs when their alignments fit DUMP_ALIGNMENT_BYTES, else
+    the longest prefix of a seeded permutation of the pairs that does.  Ranks
+    of a multi-GPU run write <name>_rank<r>.npy."""
+    os.makedirs(path, exist_ok=True)
+    sfx = f"_rank{rank}" if world > 1 else ""
+    results = np.array([[float(getattr(r, f)) for f in DUMP_RESULT_FIELDS] for r in res], np.float64).reshape(
+        len(res), len(DUMP_RESULT_FIELDS))
+    wide = any(max(r.n_steps, r.start_i + r.n_steps, r.start_j + r.n_steps) >= 1 << 24 for r in res)
+    dt = np.float64 if wide else np.float32
+    row_bytes = 3 * np.dtype(dt).itemsize
+    order = list(range(len(res)))
+    if sum(r.n_steps for r in res) * row_bytes > DUMP_ALIGNMENT_BYTES:
+        order = [int(p) for p in np.random.default_rng(0x5EED).permutation(len(res))]
+    picked, rows = [], 0
+    for p in order:
+        if (rows + res[p].n_steps) * row_bytes > DUMP_ALIGNMENT_BYTES:
+            break
+        picked.append(p)
+        rows += res[p].n_steps
+    offsets = [0]
+    alignment = np.zeros((rows, 3), dt)
+    for p in picked:
+        st = staged.steps(p)
+        if len(st) != res[p].n_steps:
+            raise RuntimeError(f"pair {p}: {len(st)} alignment steps for n_steps = {res[p].n_steps}")
+        a, b = offsets[-1], offsets[-1] + len(st)
+        alignment[a:b, 0], alignment[a:b, 1], alignment[a:b, 2] = st["choice"], st["i"], st["j"]
+        offsets.append(b)
+    for name, arr in (("results", results), ("alignment", alignment),
+                      ("alignment_pairs", np.array(picked, np.float64)),
+                      ("alignment_offsets", np.array(offsets, np.float64))):
+        np.save(os.path.join(path, f"{name}{sfx}.npy"), arr)
+
+
 def golden_digests(rank: int, P: int, L: int, related: bool = False):
     """{pair index on this rank: oracle digest} from tests/golden/synthetic(_related)_L{L}.json
     (score, statistics, alignment sha256, plane checksums), and the file's path."""
@@ -677,6 +736,12 @@ def main():
     ap.add_argument("--pairs-per-gpu", type=int,
                     default=int(os.environ["GX_BENCH_PAIRS"]) if "GX_BENCH_PAIRS" in os.environ else None,
                     help="default: as many as fill ~220 GB with score planes (80 compact / 20 int32 at 30k)")
+    ap.add_argument("--full", action="store_true",
+                    help="also everything beside the headline figure: parity against the oracle digests, the "
+                         "batch with other plane formats, the single pair, configs 2 and 3, the local batch, the "
+                         "CPU baselines (each still has its own switch below)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's per-pair results and labelled alignments as DIR/<name>.npy")
     ap.add_argument("--length", type=int, default=30000)
     ap.add_argument("--local", action="store_true", help="Smith-Waterman mode (default: global NW)")
     ap.add_argument("--no-planes", action="store_true", help="score+traceback only (not the headline)")
@@ -709,6 +774,11 @@ def main():
     ap.add_argument("--local-batch-steps", type=int, default=3,
                     help="synthetic, 1 GPU: also time a local (SW) batch of 32 related 30k pairs (0: skip)")
     args = ap.parse_args()
+    if not args.full:
+        # a plain run: the headline figure only
+        args.no_verify = args.no_cpu_baseline = True
+        args.config_steps = args.single_pair_steps = args.int32_steps = 0
+        args.no_plane_steps = args.local_batch_steps = 0
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -783,12 +853,16 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     finfo = ctx.fill_info()
-    # every timed pass's results against the oracle digests (after the timed region)
     timed_passes = staged.pass_results()
     if len(timed_passes) != args.steps:
         raise RuntimeError(f"{len(timed_passes)} pass records for {args.steps} timed steps")
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, staged, res, rank, world)
+    # --full: every timed pass's results against the oracle digests (after the timed region)
     timed_checked = 0
-    if args.workload == "synthetic" and not args.local and not args.no_verify:
+    if not args.full:
+        pass    # a plain run checks nothing
+    elif args.workload == "synthetic" and not args.local and not args.no_verify:
         mine, _ = golden_digests(rank, P, L, args.related)
         if mine:
             timed_checked = check_passes(timed_passes, mine, rank, P, "timed passes")

@@ -6,7 +6,7 @@ cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/configs
 rm -rf "$O" && mkdir -p "$O"
 run() {   # name, bench args
-  timeout -k 10 400 python bench.py "${@:2}" --no-cpu-baseline --int32-steps 0 --no-plane-steps 0 \
+  timeout -k 10 400 python bench.py --full "${@:2}" --no-cpu-baseline --int32-steps 0 --no-plane-steps 0 \
       > "$O/$1.json" 2> "$O/$1.err" || { echo BENCH_FAIL $1; tail -20 "$O/$1.err"; exit 1; }
   python3 -c "import json,sys;d=json.load(open('$O/$1.json'))
 if 'roofline' not in d: print('$1', d.get('predicted'), 'parity', d.get('parity', {}).get('pair_passes_checked')); sys.exit()

@@ -4,7 +4,7 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out/gw
 one() {   # name env -- bench args
   local name=$1 envv=$2; shift 2
-  env $envv timeout -k 10 200 python3 bench.py "$@" --single-pair-steps 0 --no-cpu-baseline --int32-steps 0 --no-plane-steps 0 \
+  env $envv timeout -k 10 200 python3 bench.py --full "$@" --single-pair-steps 0 --no-cpu-baseline --int32-steps 0 --no-plane-steps 0 \
       --config-steps 0 --local-batch-steps 0 > gpurun_out/gw/$name.json 2> gpurun_out/gw/$name.err || { echo "FAIL $name"; tail -3 gpurun_out/gw/$name.err; exit 1; }
   python3 -c "import json;d=json.load(open('gpurun_out/gw/$name.json'));p=d.get('parity',{});print('$name', d['value'], d['ms_per_step'], d['roofline'].get('fill_ms_avg'), d['fill_launch'].get('band_waves'), p.get('pairs_checked'), p.get('bit_exact'), flush=True)"
 }

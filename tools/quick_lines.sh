@@ -4,7 +4,7 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out/ql
 one() {
   local name=$1; shift
-  timeout -k 10 300 python3 bench.py "$@" --single-pair-steps 0 --no-cpu-baseline --int32-steps 0 --no-plane-steps 0 \
+  timeout -k 10 300 python3 bench.py --full "$@" --single-pair-steps 0 --no-cpu-baseline --int32-steps 0 --no-plane-steps 0 \
       --config-steps 0 > gpurun_out/ql/$name.json 2> gpurun_out/ql/$name.err || { echo "FAIL $name"; tail -3 gpurun_out/ql/$name.err; exit 1; }
   python3 -c "import json;d=json.load(open('gpurun_out/ql/$name.json'));p=d.get('parity',{});lb=d.get('local_batch',{});print('$name', d['value'], d['ms_per_step'], d['roofline'].get('fill_ms_avg'), p.get('pairs_checked'), p.get('bit_exact'), 'local', lb.get('gcups'), flush=True)"
 }

@@ -7,7 +7,7 @@ cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out/wp
 one() {   # name env... -- bench args
   local name=$1; shift
   local envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
-  env "${envs[@]}" timeout -k 10 150 python3 bench.py "$@" --single-pair-steps 0 --no-cpu-baseline --int32-steps 0 \
+  env "${envs[@]}" timeout -k 10 150 python3 bench.py --full "$@" --single-pair-steps 0 --no-cpu-baseline --int32-steps 0 \
       --no-plane-steps 0 --config-steps 0 > gpurun_out/wp/$name.json 2> gpurun_out/wp/$name.err \
       || { echo "FAIL $name"; tail -5 gpurun_out/wp/$name.err; exit 1; }
   python3 -c "import json;d=json.load(open('gpurun_out/wp/$name.json'));p=d.get('parity',{});lb=d.get('local_batch',{});print('$name', d['value'], d['ms_per_step'], d['roofline'].get('fill_ms_avg'), p.get('pairs_checked'), p.get('bit_exact'), 'local', lb.get('gcups'), flush=True)"
