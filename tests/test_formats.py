@@ -109,8 +109,122 @@ def _replay_rows(planes, h, g, local):
     return out
 
 
+# ---- scores whose attained differences sit on the ends of the code's fields ----
+# w16_ok admits x_S = S - I in [-16, 15] (5 signed bits) and x_D = D - I in
+# [-64, 63]; its bounds come from the range proof, and with g < 0 the proof
+# has slack ((1, -14, -1, 0) predicts -16 and attains -15), so the low end is
+# pinned with g = 0.  (-15, -16, 0, -15): s_match - 2g < 0 keeps the global
+# twin off its score tables (gx_api_fill.cpp twin_tbl) and gives the local
+# twin K = 16.  The last row is the default (config.toml).
+EDGE_SCORES = [(15, -1, 0, 0), (-15, -16, 0, -15), (0, -16, 0, 0), (1, -1, -1, -6), (1, -2, -1, -5)]
+# attained (x_S min, x_S max, x_D min, x_D max) over edge_family(200, 260), global / local
+EDGE_ATTAINED = {
+    ((15, -1, 0, 0), False): (-16, 15, -15, 15), ((15, -1, 0, 0), True): (-16, 15, -15, 15),
+    ((-15, -16, 0, -15), False): (-16, 15, 0, 0), ((-15, -16, 0, -15), True): (-16, -15, 0, 0),   # (local: K = 16)
+    ((1, -2, -1, -5), False): (-3, 13, -8, 8), ((1, -2, -1, -5), True): (-3, 13, -8, 8),
+    ((0, -16, 0, 0), False): (-16, 0, 0, 0), ((0, -16, 0, 0), True): (-16, 0, 0, 0),
+    ((1, -1, -1, -6), False): (-2, 15, -9, 9), ((1, -1, -1, -6), True): (-2, 15, -9, 9),
+}
+ONE_PAST_SCORES = [(2, -2, -1, -6), (1, -9, 0, -7)]   # w16_ok false, d8_planes_ok true: byte planes
+EDGE_KINDS = ("acgt", "ac", "acgtn", "related", "all_match", "all_mismatch")
+EDGE_SHAPES = [(1, 1), (64, 17), (129, 300), (257, 256), (300, 130), (200, 260), (640, 129)]
+
+
+def edge_family(n, m):
+    """kind -> (rows, columns) at n x m: random ACGT, AC and ACGTN, a related
+    pair (the rows' sequence cut or extended to m columns, m / 8 positions
+    redrawn), all-match and all-mismatch.  The GPU tests of the field edges
+    (tests/test_gpu_score_edges.py) draw their batches from it."""
+    rng = np.random.default_rng([n, m, 2024])
+    draw = lambda al, k: bytes(rng.choice(list(al), size=k).astype(np.uint8))
+    out = {"acgt": (draw(b"ACGT", n), draw(b"ACGT", m)), "ac": (draw(b"AC", n), draw(b"AC", m)),
+           "acgtn": (draw(b"ACGTN", n), draw(b"ACGTN", m))}
+    a = draw(b"ACGT", n)
+    b = bytearray((a + draw(b"ACGT", max(m - n, 0)))[:m])
+    for j in rng.integers(0, m, size=(m + 7) // 8):
+        b[int(j)] = int(rng.choice(list(b"ACGT")))
+    out["related"] = (a, bytes(b))
+    out["all_match"] = (b"A" * n, b"A" * m)
+    out["all_mismatch"] = (b"A" * n, b"C" * m)
+    return out
+
+
+def edge_batch(kinds=EDGE_KINDS):
+    """The GPU tests' batch: two pairs of every EDGE_SHAPES shape and a third
+    of 200 x 260, the kinds dealt round-robin.  The odd count leaves one pair
+    twinned with itself, and the neighbours in twin_table's order (by m, then
+    n) include twins of unequal shapes."""
+    fams = {s: edge_family(*s) for s in EDGE_SHAPES}
+    shapes = [s for s in EDGE_SHAPES for _ in range(2)] + [(200, 260)]
+    return [fams[s][kinds[k % len(kinds)]] for k, s in enumerate(shapes)]
+
+
+def _x_ranges(oracle, pairs, scores, is_local):
+    lo_s = lo_d = 1 << 60
+    hi_s = hi_d = -(1 << 60)
+    for a, b in pairs:
+        o = oracle.align(a, b, scores, is_local=is_local, want_planes=True)
+        I_pl, D_pl, S_pl = (np.asarray(p, np.int64)[1:, 1:] for p in o.planes)
+        xS, xD = S_pl - I_pl, D_pl - I_pl
+        lo_s, hi_s = min(lo_s, int(xS.min())), max(hi_s, int(xS.max()))
+        lo_d, hi_d = min(lo_d, int(xD.min())), max(hi_d, int(xD.max()))
+    return lo_s, hi_s, lo_d, hi_d
+
+
+@pytest.mark.parametrize("scores,is_local", sorted(EDGE_ATTAINED))
+def test_edge_scores_attain_field_ends(oracle, scores, is_local):
+    """Over the 200 x 260 family the oracle's planes attain exactly the ends
+    of the 5-bit x_S field (the sign-extension case code & 31 == 16 and the
+    top, 15) that the GPU tests claim to exercise, inside an admitted rule."""
+    assert _w16_ok(*scores)
+    assert _x_ranges(oracle, edge_family(200, 260).values(), scores, is_local) == EDGE_ATTAINED[scores, is_local]
+
+
+@pytest.mark.parametrize("scores,is_local", sorted(EDGE_ATTAINED))
+@pytest.mark.parametrize("alphabet", ["five_symbols", "four_symbols"])
+def test_edge_batches_attain_field_ends(oracle, scores, is_local, alphabet):
+    """The same for the batches the GPU tests run (all EDGE_SHAPES): with the
+    ACGTN pairs (the plain match test) and without them (<= 4 symbols: the
+    score tables)."""
+    kinds = EDGE_KINDS if alphabet == "five_symbols" else tuple(k for k in EDGE_KINDS if k != "acgtn")
+    assert _x_ranges(oracle, edge_batch(kinds), scores, is_local) == EDGE_ATTAINED[scores, is_local]
+
+
+def test_field_edge_is_sharp(oracle):
+    """(2, -2, -1, -6) lies one past the rule (x_S up to 16) and the inputs
+    reach it: the codec decodes those cells wrongly, so w16_ok must refuse it
+    (the GPU run then keeps byte planes)."""
+    scores = (2, -2, -1, -6)
+    assert not _w16_ok(*scores) and _ranges(*scores)[1][1] == 16
+    hit = 0
+    for a, b in edge_family(200, 260).values():
+        o = oracle.align(a, b, scores, want_planes=True)
+        I_pl, D_pl, S_pl = (np.asarray(p, np.int64)[1:, 1:] for p in o.planes)
+        xS, xD = S_pl - I_pl, D_pl - I_pl
+        assert xS.max() <= 16
+        at = xS == 16
+        hit += int(at.sum())
+        dS, dD = _decode(_encode(I_pl, D_pl, S_pl))
+        assert not np.any((dS == xS)[at]), "a 5-bit field cannot hold 16"
+        assert np.array_equal(dS[~at], xS[~at])
+    assert hit > 0
+    # (1, -9, 0, -7): refused at the proved low bound, -17
+    assert not _w16_ok(1, -9, 0, -7) and _ranges(1, -9, 0, -7)[1][0] == -17
+
+
+def test_format_routing_on_the_host(gx):
+    """gx_plane_bytes_per_cell (d8_planes_ok): byte planes up to U - 2a = 127,
+    and for the scores one past the twin codes' fields; int32 planes beyond."""
+    assert _ranges(1, -1, 0, -42)[2] == (-127, 127) and _ranges(1, -1, 0, -43)[2][1] == 130
+    for scores in [(1, -1, 0, -42)] + ONE_PAST_SCORES:
+        for loc in (False, True):
+            assert gx.plane_bytes_per_cell(gx.Scores(*scores), loc) == 3, (scores, loc)
+    for loc in (False, True):
+        assert gx.plane_bytes_per_cell(gx.Scores(1, -1, 0, -43), loc) == 12
+
+
 @pytest.mark.parametrize("scores", [(1, -2, -1, -5), (1, -2, -2, -5), (2, -3, -1, -4), (1, -1, 0, 0),
-                                    (3, -3, -1, -1)])
+                                    (3, -3, -1, -1)] + EDGE_SCORES[:-1])
 @pytest.mark.parametrize("is_local", [False, True], ids=["global", "local"])
 def test_insert_replay_matches_oracle(oracle, scores, is_local):
     """The decoders' replay of I along a row equals the oracle's insert

@@ -252,7 +252,8 @@ def test_twin_pairs_by_shape(gx, ctx, oracle, monkeypatch):
 # kernel (GX_TABLE_TWIN), and the alignment, against the oracle.
 from test_twin_bound import _families  # noqa: E402
 
-BOUND_SCORES = [(CONFIG_SCORES, 15), ((1, -1, -1, -7), 15), ((1, -1, -1, -16), 8), ((2, -2, -1, -34), 4)]
+BOUND_SCORES = [(CONFIG_SCORES, 15), ((1, -1, -1, -7), 15), ((1, -1, -1, -16), 8), ((2, -2, -1, -34), 4),
+                ((1, -1, 0, -20), 7), ((1, -1, 0, -42), 3)]
 
 
 @pytest.mark.parametrize("scores,W", BOUND_SCORES)
@@ -298,6 +299,27 @@ def test_twin_bound_worst_inputs_batch(gx, ctx, oracle, monkeypatch, scores, W):
         for k in range(2):
             assert [int(x) for x in sums[k, p]] == o.extra["plane_sums"], (scores, p, k)
         assert res[p].score == o.score and _steps_list(st.steps(p)) == o.alignment(), (scores, p)
+
+
+@pytest.mark.parametrize("scores,twin", [((1, -1, 0, -49), 1), ((1, -1, 0, -50), 0)], ids=["h49", "h50"])
+def test_twin_bound_traceback_only(gx, ctx, oracle, monkeypatch, scores, twin):
+    """The widest scores the narrowest band width admits, (1, -1, 0, -49) at
+    W = 3, on the worst inputs: past the byte planes' range (d8_planes_ok), so
+    only the traceback-only twin fill (gx_align_batch, no planes) runs them.
+    One step further, (1, -1, 0, -50), no width is admitted: the scalar fill.
+    Every alignment and statistic."""
+    monkeypatch.setenv("GX_LAYOUT", "0")
+    monkeypatch.setenv("GX_BAND_WAVES", "3")
+    fam = _families(128 * 3 * 2 + 300, 1400)
+    pairs = [fam[k] for k in ("all_mismatch", "all_match", "gap_rows", "gap_cols", "repeat")]
+    out = gx.align_batch(pairs, gx.Scores(*scores), False, ctx=ctx, max_cell=False)
+    info = ctx.fill_info()
+    assert info["twin"] == twin and (not twin or info["band_waves"] == 3), info
+    for (a, b), (steps, r) in zip(pairs, out):
+        o = oracle.align(a, b, scores)
+        assert _steps_list(steps) == o.alignment(), (scores, len(a), len(b))
+        assert (r.score, r.matches, r.mismatches, r.gap_extensions, r.opening_gaps, r.n_steps) == \
+               (o.score, o.matches, o.mismatches, o.gap_extensions, o.opening_gaps, len(o.choices)), (scores, len(a))
 
 
 @pytest.mark.parametrize("m", [31920, 65536])

@@ -92,7 +92,10 @@ def _max_spread_ratio(planes, g, W, dm, local=False):
 # W = 15, D = 19 at W = 8, D = 38 at W = 4: the largest neighbour differences
 # the rule lets through); a wide-gap and a match-heavy scoring
 SCORES = [(CONFIG_SCORES, 15), ((1, -1, -1, -7), 15), ((1, -1, -1, -16), 8), ((2, -2, -1, -34), 4),
-          ((5, -4, 0, -10), 8), ((1, -2, -2, -5), 15)]
+          ((5, -4, 0, -10), 8), ((1, -2, -2, -5), 15),
+          # D = 21: the widest W = 7 admits ((1, -1, 0, -21) drops to 4); D = 43: a W = 3 twin and the last
+          # scores of the byte planes (d8_planes_ok, U - 2a = 127); D = 50: the widest W = 3 admits
+          ((1, -1, 0, -20), 7), ((1, -1, 0, -42), 3), ((1, -1, 0, -49), 3)]
 
 
 @pytest.mark.parametrize("scores,W", SCORES)
@@ -101,12 +104,22 @@ def test_admission_rule_matches_width(gx, scores, W):
     itself, and not the next wider instantiated width."""
     ok, bound = gx.twin_admission(gx.Scores(*scores), W, 0)
     assert ok and bound < 30000, (scores, W, bound)
-    wider = {4: 7, 7: 8, 8: 15}.get(W)
+    wider = {3: 4, 4: 7, 7: 8, 8: 15}.get(W)
     if wider:
         assert not gx.twin_admission(gx.Scores(*scores), wider, 0)[0], (scores, wider)
     d = _neighbour_d(scores)
     sm, smm, g, h = scores
     assert bound == d * (192 * W + 16) + 2 * (abs(h + g) + abs(max(sm, smm)) + abs(min(sm, smm))) + 64
+
+
+def test_admission_width_edges(gx):
+    """One step past the widest scores of W = 7 and of W = 3, the narrowest
+    instantiated width: (1, -1, 0, -21) drops to W = 4, (1, -1, 0, -50) is
+    admitted at no width (run_fill then keeps the scalar fill)."""
+    assert not gx.twin_admission(gx.Scores(1, -1, 0, -21), 7, 0)[0]
+    assert gx.twin_admission(gx.Scores(1, -1, 0, -21), 4, 0)[0]
+    ok, bound = gx.twin_admission(gx.Scores(1, -1, 0, -50), 3, 0)
+    assert not ok and bound >= 30000, bound
 
 
 def test_admission_column_gap(gx):
