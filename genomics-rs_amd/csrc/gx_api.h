@@ -7,6 +7,7 @@
 //   gx_api_table.cpp    alignment_table / retrace (algo.rs:151-441), table export
 //   gx_api_batch.cpp    batches of independent pairs, multi-context batches
 //   gx_api_staged.cpp   device-resident (staged) batches, the benchmark path
+//   gx_api_compare.cpp  compare mode: longest-common-substring recursion (main.rs:216-379)
 // Not a public header: host code only, one library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -318,6 +319,10 @@ struct gx_context {
     bool keep_capture = false;
     HostScores kept_hs{};
     Scores32 kept_sc{};
+    // the last compare call (gx_compare_info, gx_compare_run_stats; gx_api_compare.cpp)
+    uint64_t cmp_gpu = 0, cmp_host = 0, cmp_ovf = 0, cmp_levels = 0;
+    uint64_t cmp_cells = 0;      // byte compares of its run-kernel launches
+    double cmp_run_ms = 0.0;     // ... and their device time
 };
 
 struct PairHost {

@@ -18,6 +18,17 @@
 //       processing-time on n*m, one host thread and gx_context per GPU, one
 //       batched launch per GPU.  Files are read in name order (the reference
 //       uses fs::read_dir order, which the OS leaves unspecified).
+//
+//   gx-align compare -d fasta_dir [-o similarity_matrix.tsv]
+//       main.rs:216-379: the similarity matrix of the records of all *.fasta
+//       files in fasta_dir (name order, as all-vs-all) -- element [j][i], i <= j,
+//       is the sum of longest-common-substring lengths over the reference's
+//       recursion (gx_compare_matrix) -- written as similarity_matrix.tsv and
+//       printed as the "Similarity TSV" and "LCS Length TSV" blocks
+//       (main.rs:330-378).  The alphabet file, suffix-link and thread options
+//       configure the reference's suffix tree and thread pool and have no
+//       counterpart; its coloured overview (comparison/display.rs) is not
+//       printed.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -39,7 +50,8 @@ void usage() {
     fprintf(stderr,
             "Usage: gx-align [-c|--config-path <CONFIG>] align [-a|--alignment-type <TYPE>] -f|--fasta-path <FASTA>\n"
             "       gx-align [-c|--config-path <CONFIG>] all-vs-all -d|--fasta-dir <DIR> [-a <TYPE>] "
-            "[-o <TSV>] [-g|--gpus <N>] [--no-self]\n");
+            "[-o <TSV>] [-g|--gpus <N>] [--no-self]\n"
+            "       gx-align compare -d|--fasta-dir <DIR> [-o <TSV>]\n");
 }
 
 struct Records {
@@ -283,6 +295,67 @@ int run_all_vs_all(const gx_scores& sc, const std::string& type, const std::stri
     return 0;
 }
 
+// Command::Compare (main.rs:216-379) on GPU 0.
+int run_compare(const std::string& dir, const std::string& tsv) {
+    namespace fs = std::filesystem;
+    std::vector<std::string> files;
+    std::error_code ec;
+    for (const auto& e : fs::directory_iterator(dir, ec))
+        if (e.path().extension() == ".fasta") files.push_back(e.path().string());
+    if (ec) { fprintf(stderr, "[ERROR] cannot read directory %s: %s\n", dir.c_str(), ec.message().c_str()); return 1; }
+    std::sort(files.begin(), files.end());
+    const char* lg = getenv("GX_LOG");
+    const bool info = lg && (!strcmp(lg, "info") || !strcmp(lg, "debug"));
+    if (info) fprintf(stderr, "[INFO] MODE: Compare\n[INFO] FASTA directory: %s\n[INFO] Loading sequences from %s\n",
+                      dir.c_str(), dir.c_str());
+    Records r;
+    for (const auto& f : files) load_fasta(f, r);
+    const size_t K = r.size();
+    if (info) fprintf(stderr, "[INFO] Number of sequences: %zu\n", K);
+    gx_context* ctx = nullptr;
+    if (gx_context_create(0, &ctx) != GX_OK) return fail_msg("context", 1);
+    std::vector<const uint8_t*> seqs(K);
+    std::vector<size_t> lens(K);
+    for (size_t k = 0; k < K; ++k) { seqs[k] = r.seq(k); lens[k] = r.sl[k]; }
+    std::vector<gx_compare_cell> mat(K * K);
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = gx_compare_matrix(ctx, seqs.data(), lens.data(), K, mat.data());
+    const auto us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+    if (rc != GX_OK) { gx_context_destroy(ctx); return fail_msg("compare", rc); }
+    if (info) {
+        uint64_t ng = 0, nh = 0, no = 0, nl = 0;
+        gx_compare_info(ctx, &ng, &nh, &no, &nl);
+        fprintf(stderr, "[INFO] [FindPath] Time taken to compare: %lld us (%lld ms)\n", (long long)us,
+                (long long)(us / 1000));
+        fprintf(stderr, "[INFO] %llu sub-problems on the GPU in %llu levels, %llu on the host (%llu overflowed)\n",
+                (unsigned long long)ng, (unsigned long long)nl, (unsigned long long)nh, (unsigned long long)no);
+    }
+    gx_context_destroy(ctx);
+    FILE* f = fopen(tsv.c_str(), "w");
+    if (!f) { fprintf(stderr, "[ERROR] cannot write %s\n", tsv.c_str()); return 1; }
+    // main.rs:337-378: the file and the first stdout block carry the score, the second block first_lcs_length
+    auto table = [&](FILE* o, bool header_blank, bool lcs) {
+        fprintf(o, header_blank ? " \t" : "\t");
+        for (size_t i = 0; i < K; ++i) fprintf(o, "%zu\t", i);
+        fprintf(o, "\n");
+        for (size_t j = 0; j < K; ++j) {
+            fprintf(o, "%zu\t", j);
+            for (size_t i = 0; i < K; ++i) {
+                const gx_compare_cell& c = mat[j * K + i];
+                fprintf(o, "%llu\t", (unsigned long long)(lcs ? c.first_lcs : c.score));
+            }
+            fprintf(o, "\n");
+        }
+    };
+    table(f, false, false);
+    fclose(f);
+    printf("Similarity TSV:\n");
+    table(stdout, true, false);
+    printf("\nLCS Length TSV:\n");
+    table(stdout, true, true);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -298,7 +371,7 @@ int main(int argc, char** argv) {
             dst = argv[++k];
         };
         if (a == "-c" || a == "--config-path") next(config);
-        else if (a == "align" || a == "all-vs-all") mode = a;
+        else if (a == "align" || a == "all-vs-all" || a == "compare") mode = a;
         else if (a == "-a" || a == "--alignment-type") next(type);
         else if (a == "-f" || a == "--fasta-path") next(fasta);
         else if (a == "-d" || a == "--fasta-dir") next(dir);
@@ -308,10 +381,11 @@ int main(int argc, char** argv) {
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else { usage(); return 2; }
     }
-    if (mode.empty() || (mode == "align" && fasta.empty()) || (mode == "all-vs-all" && dir.empty())) {
+    if (mode.empty() || (mode == "align" && fasta.empty()) || (mode != "align" && dir.empty())) {
         usage();
         return 2;
     }
+    if (mode == "compare") return run_compare(dir, tsv);   // (reads no scores: main.rs:216-221)
     gx_scores sc;
     if (gx_config_load(config.c_str(), &sc) != GX_OK) {
         fprintf(stderr, "[ERROR] %s\n", gx_last_error());

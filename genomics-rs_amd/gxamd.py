@@ -59,6 +59,11 @@ class CStep(ctypes.Structure):
                 ("i", ctypes.c_uint64), ("j", ctypes.c_uint64)]
 
 
+class CCompareCell(ctypes.Structure):
+    _fields_ = [("score", ctypes.c_uint64), ("len_i", ctypes.c_uint64), ("len_j", ctypes.c_uint64),
+                ("first_lcs", ctypes.c_uint64)]
+
+
 class CResult(ctypes.Structure):
     _fields_ = [("score", ctypes.c_int64), ("matches", ctypes.c_uint64), ("mismatches", ctypes.c_uint64),
                 ("gap_extensions", ctypes.c_uint64), ("opening_gaps", ctypes.c_uint64),
@@ -80,7 +85,10 @@ EXPORTED = ["gx_last_error", "gx_version", "gx_context_create", "gx_context_dest
             "gx_staged_pass_results", "gx_fill_info", "gx_batch_chunks", "gx_fill_twin", "gx_fill_groups", "gx_fill_plane_bits", "gx_plane_bytes_per_cell", "gx_twin_admission",
             "gx_twin_admission_mode", "gx_plan_layout", "gx_staged_table",
             "gx_fasta_load",
-            "gx_config_load", "gx_format_alignment", "gx_format_table"]
+            "gx_config_load", "gx_format_alignment", "gx_format_table",
+            "gx_common_substring_host", "gx_common_substring", "gx_compare_pair", "gx_compare_matrix",
+            "gx_compare_info", "gx_compare_segment_height", "gx_compare_run_stats",
+            "gx_common_substring_candidates_host"]
 
 _lib = None
 
@@ -142,6 +150,15 @@ def lib():
     L.gx_config_load.argtypes = [ctypes.c_char_p, ctypes.POINTER(CScores)]
     L.gx_format_alignment.argtypes = [vp, sz, vp, sz, vp, sz, ctypes.POINTER(CResult), vp, sz, ctypes.POINTER(sz)]
     L.gx_format_table.argtypes = [vp, sz, vp, sz, vp, sz, vp, vp, vp, ctypes.c_int, vp, sz, ctypes.POINTER(sz)]
+    u64p = ctypes.POINTER(ctypes.c_uint64)
+    L.gx_common_substring_host.argtypes = [vp, sz, vp, sz, u64p, u64p, u64p]
+    L.gx_common_substring_candidates_host.argtypes = [vp, sz, vp, sz, u64p, u64p]
+    L.gx_common_substring.argtypes = [vp, vp, sz, vp, sz, u64p, u64p, u64p]
+    L.gx_compare_pair.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(CCompareCell), u64p]
+    L.gx_compare_matrix.argtypes = [vp, vp, vp, sz, vp]
+    L.gx_compare_info.argtypes = [vp, u64p, u64p, u64p, u64p]
+    L.gx_compare_segment_height.argtypes = []
+    L.gx_compare_run_stats.argtypes = [vp, u64p, ctypes.POINTER(ctypes.c_double)]
     _lib = L
     return L
 
@@ -796,3 +813,75 @@ def similarity_tsv(result: dict, field: str = "score", blank_header: bool = Fals
     for r in range(k):
         out.append(f"{r}\t" + "".join(f"{cell.get((r, c), 0)}\t" for c in range(k)) + "\n")
     return "".join(out)
+
+
+# ---------------------------------------------------------------------------
+# compare mode (main.rs:216-379)
+
+def common_substring_host(a: bytes, b: bytes) -> Tuple[int, int, int]:
+    """get_lcs(0, 1) (tree.rs:218-281) of a then b on the host solver, no device: (i, j, L)."""
+    ka, pa = _buf(a)
+    kb, pb = _buf(b)
+    i, j, n = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    _check(lib().gx_common_substring_host(pa, len(a), pb, len(b), ctypes.byref(i), ctypes.byref(j), ctypes.byref(n)))
+    return i.value, j.value, n.value
+
+
+def common_substring_candidates_host(a: bytes, b: bytes) -> Tuple[int, int]:
+    """(L, number of (i, j) starts of common substrings of length L), host solver."""
+    ka, pa = _buf(a)
+    kb, pb = _buf(b)
+    n, c = ctypes.c_uint64(), ctypes.c_uint64()
+    _check(lib().gx_common_substring_candidates_host(pa, len(a), pb, len(b), ctypes.byref(n), ctypes.byref(c)))
+    return n.value, c.value
+
+
+def common_substring(a: bytes, b: bytes, ctx: Optional["Context"] = None) -> Tuple[int, int, int]:
+    """get_lcs(0, 1) of a then b on the GPU: (i, j, L)."""
+    ctx = ctx or default_context()
+    ka, pa = _buf(a)
+    kb, pb = _buf(b)
+    i, j, n = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+    _check(lib().gx_common_substring(ctx.ptr, pa, len(a), pb, len(b), ctypes.byref(i), ctypes.byref(j),
+                                     ctypes.byref(n)))
+    return i.value, j.value, n.value
+
+
+def compare_pair(a: bytes, b: bytes, ctx: Optional["Context"] = None, host: bool = False) -> Tuple[int, int, int]:
+    """One similarity-matrix element (main.rs:281-315): (score, first_lcs, get_matches calls).
+    host=True runs the recursion on the host solver with no device."""
+    ptr = None if host else (ctx or default_context()).ptr
+    ka, pa = _buf(a)
+    kb, pb = _buf(b)
+    cell, calls = CCompareCell(), ctypes.c_uint64()
+    _check(lib().gx_compare_pair(ptr, pa, len(a), pb, len(b), ctypes.byref(cell), ctypes.byref(calls)))
+    return cell.score, cell.first_lcs, calls.value
+
+
+def compare_matrix(seqs: Seq[bytes], ctx: Optional["Context"] = None, host: bool = False) -> np.ndarray:
+    """The similarity matrix (main.rs:241-316) as uint64 [nseq][nseq][4]: element [j][i], i <= j, holds
+    (score, len_i, len_j, first_lcs); the other half is zero."""
+    ptr = None if host else (ctx or default_context()).ptr
+    k = len(seqs)
+    keep = [_buf(s) for s in seqs]
+    ptrs = (ctypes.c_void_p * max(k, 1))(*[p for _, p in keep])
+    lens = (ctypes.c_size_t * max(k, 1))(*[len(s) for s in seqs])
+    out = np.zeros((k, k, 4), np.uint64)
+    _check(lib().gx_compare_matrix(ptr, ptrs, lens, k, out.ctypes.data))
+    return out
+
+
+def compare_info(ctx: Optional["Context"] = None) -> dict:
+    """gx_compare_info / gx_compare_run_stats of the last compare call on ctx."""
+    ctx = ctx or default_context()
+    v = [ctypes.c_uint64() for _ in range(5)]
+    ms = ctypes.c_double()
+    _check(lib().gx_compare_info(ctx.ptr, *[ctypes.byref(x) for x in v[:4]]))
+    _check(lib().gx_compare_run_stats(ctx.ptr, ctypes.byref(v[4]), ctypes.byref(ms)))
+    return {"gpu_subproblems": v[0].value, "host_subproblems": v[1].value, "overflowed": v[2].value,
+            "levels": v[3].value, "byte_compares": v[4].value, "run_ms": ms.value}
+
+
+def compare_segment_height() -> int:
+    """Rows per segment of the run kernel's tiles (gx_compare_segment_height)."""
+    return lib().gx_compare_segment_height()

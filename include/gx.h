@@ -323,6 +323,61 @@ int gx_format_table(const uint8_t* s1, size_t n, const uint8_t* s2, size_t m, co
                     const int64_t* insert_plane, const int64_t* delete_plane, const int64_t* sub_plane, int color,
                     char* out, size_t cap, size_t* needed);
 
+/* ---- compare mode (main.rs:216-379) --------------------------------------
+ * The reference builds a generalized suffix tree per get_matches call; the
+ * quantity it reads off the tree is the longest run of equal bytes along a
+ * diagonal of the comparison grid, which the GPU computes directly
+ * (DESIGN.md 16).  Input bytes must be above '$' (0x24): at or below it they
+ * collide with the reference's terminators ('$', '!') -> GX_EINVAL.
+ * Sequences of 2^30 bytes or more -> GX_ERANGE. */
+
+/* One element of the similarity matrix: the tuple (score, len_i, len_j,
+ * first_lcs_length) of main.rs:310-315. */
+typedef struct gx_compare_cell { uint64_t score, len_i, len_j, first_lcs; } gx_compare_cell;
+
+/* get_lcs(0, 1) (tree.rs:218-281) on a tree holding a then b, on the host with
+ * no device: *len = the longest common substring's length L, W = the
+ * lexicographically smallest common substring of that length (the DFS visits
+ * children in alphabet order, tree.rs:444-464, and keeps the first deepest
+ * node), *i / *j = the start of the smallest suffix of a + '$' / b + '!' that
+ * begins with W (the first leaf below the node).  L = 0 gives (0, 0, 0). */
+int gx_common_substring_host(const uint8_t* a, size_t n, const uint8_t* b, size_t m,
+                             uint64_t* i, uint64_t* j, uint64_t* len);
+/* The same on the GPU (one sub-problem, no recursion). */
+int gx_common_substring(gx_context* ctx, const uint8_t* a, size_t n, const uint8_t* b, size_t m,
+                        uint64_t* i, uint64_t* j, uint64_t* len);
+/* One matrix element (main.rs:281-315): first_lcs = L of (a, b); score = the
+ * sum of L over the traversal that recurses on (a[..i], b[..j]) and
+ * (a[i+L..], b[j+L..]) while L > 0.  *n_calls (may be NULL) = get_matches
+ * calls (main.rs:267-279), empty pieces included.  ctx = NULL runs the whole
+ * recursion on the host solver. */
+int gx_compare_pair(gx_context* ctx, const uint8_t* a, size_t n, const uint8_t* b, size_t m,
+                    gx_compare_cell* out, uint64_t* n_calls);
+/* The similarity matrix (main.rs:241-316): out[j * nseq + i] for i <= j, the
+ * other half zero as the reference leaves it.  The sequences are staged on
+ * the device once and the recursions of all pairs advance level by level,
+ * one batch of launches per level.  ctx = NULL: host solver only. */
+int gx_compare_matrix(gx_context* ctx, const uint8_t* const* seqs, const size_t* lens, size_t nseq,
+                      gx_compare_cell* out);
+/* The last compare call on ctx: sub-problems answered by the kernels, by the
+ * host solver (those below GX_COMPARE_HOST_CELLS cells with everything under
+ * them, and the overflowed ones), sub-problems whose candidate buffer
+ * overflowed (GX_COMPARE_CAND_CAP), and levels that launched.  No reference
+ * counterpart (measurement only). */
+int gx_compare_info(const gx_context* ctx, uint64_t* gpu_subproblems, uint64_t* host_subproblems,
+                    uint64_t* overflowed, uint64_t* levels);
+/* Rows per segment of the run kernel's tiles: diagonals are
+ * cut every this many rows of a.  Measurement and tests only. */
+int gx_compare_segment_height(void);
+/* Byte compares and device time (ms) of the run-kernel launches of the last
+ * compare call on ctx.  Measurement only. */
+int gx_compare_run_stats(const gx_context* ctx, uint64_t* byte_compares, double* run_ms);
+/* L and the number of (i, j) starts of common substrings of that length, from
+ * the host solver: what the candidate buffer of a sub-problem would have to
+ * hold (the measurement behind GX_COMPARE_CAND_CAP's default). */
+int gx_common_substring_candidates_host(const uint8_t* a, size_t n, const uint8_t* b, size_t m,
+                                        uint64_t* len, uint64_t* n_candidates);
+
 #ifdef __cplusplus
 }
 #endif
