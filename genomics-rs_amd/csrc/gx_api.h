@@ -8,6 +8,7 @@
 //   gx_api_batch.cpp    batches of independent pairs, multi-context batches
 //   gx_api_staged.cpp   device-resident (staged) batches, the benchmark path
 //   gx_api_compare.cpp  compare mode: longest-common-substring recursion (main.rs:216-379)
+//   gx_api_suffix.cpp   suffix-tree mode: BWT and tree statistics from the suffix array (main.rs:154-215)
 // Not a public header: host code only, one library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -323,6 +324,9 @@ struct gx_context {
     uint64_t cmp_gpu = 0, cmp_host = 0, cmp_ovf = 0, cmp_levels = 0;
     uint64_t cmp_cells = 0;      // byte compares of its run-kernel launches
     double cmp_run_ms = 0.0;     // ... and their device time
+    // the last suffix-tree call (gx_suffix_info; gx_api_suffix.cpp)
+    uint64_t suf_rounds = 0, suf_passes = 0;
+    double suf_sort_ms = 0.0, suf_lcp_ms = 0.0, suf_fold_ms = 0.0;
 };
 
 struct PairHost {

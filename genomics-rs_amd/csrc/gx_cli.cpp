@@ -29,6 +29,14 @@
 //       configure the reference's suffix tree and thread pool and have no
 //       counterpart; its coloured overview (comparison/display.rs) is not
 //       printed.
+//
+//   gx-align suffix-tree -f file.fasta [-a alphabet.txt] [--suffix-links] [--stats] [-o bwt.txt]
+//       main.rs:154-215: the suffix tree of the file's first record, read off
+//       its suffix array (gx_suffix_tree_stats).  With --stats the BWT is
+//       written one character per line (BWT_out/<name>_bwt.txt unless -o) and
+//       the "Stats:" block is printed.  An alphabet file, when given, is
+//       checked as the reference's tree checks it; --suffix-links is accepted
+//       and ignored; the Graphviz block of small trees is not printed.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -51,7 +59,9 @@ void usage() {
             "Usage: gx-align [-c|--config-path <CONFIG>] align [-a|--alignment-type <TYPE>] -f|--fasta-path <FASTA>\n"
             "       gx-align [-c|--config-path <CONFIG>] all-vs-all -d|--fasta-dir <DIR> [-a <TYPE>] "
             "[-o <TSV>] [-g|--gpus <N>] [--no-self]\n"
-            "       gx-align compare -d|--fasta-dir <DIR> [-o <TSV>]\n");
+            "       gx-align compare -d|--fasta-dir <DIR> [-o <TSV>]\n"
+            "       gx-align suffix-tree -f|--fasta-path <FASTA> [-a|--alphabet-file <ALPHABET>] [--suffix-links] "
+            "[--stats] [-o <BWT>]\n");
 }
 
 struct Records {
@@ -356,6 +366,78 @@ int run_compare(const std::string& dir, const std::string& tsv) {
     return 0;
 }
 
+// Command::SuffixTree (main.rs:154-215) on GPU 0: the BWT and the statistics
+// of the first record's suffix tree, from its suffix array.
+int run_suffix_tree(const std::string& fasta, const std::string& alphabet, bool stats, std::string bwt_path) {
+    namespace fs = std::filesystem;
+    const char* lg = getenv("GX_LOG");
+    const bool info = lg && (!strcmp(lg, "info") || !strcmp(lg, "debug"));
+    if (info) fprintf(stderr, "[INFO] MODE: Suffix Tree\n[INFO] Loading sequences from %s\n", fasta.c_str());
+    Records r;
+    load_fasta(fasta, r);
+    if (!r.size()) {
+        fprintf(stderr, "thread 'main' panicked: index out of bounds: the len is 0 but the index is 0\n");
+        return 101;  // main.rs:168 indexes sequences[0]
+    }
+    const uint8_t* s = r.seq(0);
+    const size_t n = r.sl[0];
+    if (!alphabet.empty()) {
+        // SuffixTree::new (tree.rs:138-148) and get_child_index (tree.rs:56-63)
+        FILE* f = fopen(alphabet.c_str(), "rb");
+        if (!f) { fprintf(stderr, "thread 'main' panicked: Could not read alphabet file: %s\n", alphabet.c_str()); return 101; }
+        bool in[256] = {};
+        for (const char* q = "$!@#%^&*()-_=+{}[]|;:'<>,.?/~` \n"; *q; ++q) in[(uint8_t)*q] = true;   // STRING_TERMINATORS
+        for (int c; (c = fgetc(f)) != EOF;) in[c & 255] = true;
+        fclose(f);
+        for (size_t k = 0; k < n; ++k)
+            if (!in[s[k]]) {
+                fprintf(stderr, "thread 'main' panicked: Character %c not found in alphabet\n", s[k]);
+                return 101;
+            }
+    }
+    gx_context* ctx = nullptr;
+    if (gx_context_create(0, &ctx) != GX_OK) return fail_msg("context", 1);
+    gx_suffix_stats st{};
+    std::vector<uint8_t> bwt(n + 1);
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = gx_suffix_tree_stats(ctx, s, n, &st, bwt.data(), nullptr, nullptr);
+    const auto us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+    if (rc != GX_OK) { gx_context_destroy(ctx); return fail_msg("suffix-tree", rc); }
+    if (info) {
+        uint64_t rounds = 0, passes = 0;
+        gx_suffix_info(ctx, &rounds, &passes, nullptr, nullptr, nullptr);
+        fprintf(stderr, "[INFO] [FindPath] Time taken to build suffix tree: %lld us (%lld ms)\n", (long long)us,
+                (long long)(us / 1000));
+        fprintf(stderr, "[INFO] suffix array of %zu suffixes: %llu doubling rounds, %llu radix passes\n", n + 1,
+                (unsigned long long)rounds, (unsigned long long)passes);
+    }
+    gx_context_destroy(ctx);
+    if (!stats) return 0;
+    if (bwt_path.empty()) {
+        // main.rs:181-191: the file name behind the last '/' and '\\', without ".fasta"
+        std::string name = fasta.substr(fasta.find_last_of('/') == std::string::npos ? 0 : fasta.find_last_of('/') + 1);
+        name = name.substr(name.find_last_of('\\') == std::string::npos ? 0 : name.find_last_of('\\') + 1);
+        for (size_t p; (p = name.find(".fasta")) != std::string::npos;) name.erase(p, 6);
+        bwt_path = "BWT_out/" + name + "_bwt.txt";
+    }
+    if (info) fprintf(stderr, "[INFO] BWT Path: %s\n", bwt_path.c_str());
+    std::error_code ec;
+    if (fs::path(bwt_path).has_parent_path()) fs::create_directories(fs::path(bwt_path).parent_path(), ec);
+    FILE* f = fopen(bwt_path.c_str(), "w");
+    if (!f) { fprintf(stderr, "[ERROR] cannot write %s\n", bwt_path.c_str()); return 1; }
+    std::string lines(2 * bwt.size(), '\n');   // main.rs:207-211: one character per line
+    for (size_t k = 0; k < bwt.size(); ++k) lines[2 * k] = (char)bwt[k];
+    fwrite(lines.data(), 1, lines.size(), f);
+    fclose(f);
+    size_t need = 0;
+    gx_format_suffix_stats(&st, bwt.data(), bwt.size(), nullptr, 0, &need);
+    std::vector<char> txt(need);
+    if (gx_format_suffix_stats(&st, bwt.data(), bwt.size(), txt.data(), txt.size(), nullptr) != GX_OK)
+        return fail_msg("stats", 1);
+    printf("\nStats: %s\n", txt.data());   // display.rs:54 (the Graphviz block is out of scope)
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -363,7 +445,7 @@ int main(int argc, char** argv) {
     setenv("GX_LOG", getenv("GX_LOG") ? getenv("GX_LOG") : "info", 1);
     std::string config = "config.toml", type, fasta, dir, tsv = "similarity_matrix.tsv", mode;
     int ngpu = 0;
-    bool with_self = true;
+    bool with_self = true, stats = false, out_set = false;
     for (int k = 1; k < argc; ++k) {
         std::string a = argv[k];
         auto next = [&](std::string& dst) {
@@ -371,21 +453,25 @@ int main(int argc, char** argv) {
             dst = argv[++k];
         };
         if (a == "-c" || a == "--config-path") next(config);
-        else if (a == "align" || a == "all-vs-all" || a == "compare") mode = a;
-        else if (a == "-a" || a == "--alignment-type") next(type);
+        else if (a == "align" || a == "all-vs-all" || a == "compare" || a == "suffix-tree") mode = a;
+        else if (a == "-a" || a == "--alignment-type" || a == "--alphabet-file") next(type);   // (suffix-tree: the alphabet)
         else if (a == "-f" || a == "--fasta-path") next(fasta);
         else if (a == "-d" || a == "--fasta-dir") next(dir);
-        else if (a == "-o" || a == "--output") next(tsv);
+        else if (a == "-o" || a == "--output") { next(tsv); out_set = true; }
+        else if (a == "--stats") stats = true;
+        else if (a == "--suffix-links") {}   // (the reference's build strategy: no counterpart)
         else if (a == "-g" || a == "--gpus") { std::string v; next(v); ngpu = atoi(v.c_str()); }
         else if (a == "--no-self") with_self = false;
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else { usage(); return 2; }
     }
-    if (mode.empty() || (mode == "align" && fasta.empty()) || (mode != "align" && dir.empty())) {
+    const bool by_file = mode == "align" || mode == "suffix-tree";
+    if (mode.empty() || (by_file && fasta.empty()) || (!by_file && dir.empty())) {
         usage();
         return 2;
     }
     if (mode == "compare") return run_compare(dir, tsv);   // (reads no scores: main.rs:216-221)
+    if (mode == "suffix-tree") return run_suffix_tree(fasta, type, stats, out_set ? tsv : std::string());
     gx_scores sc;
     if (gx_config_load(config.c_str(), &sc) != GX_OK) {
         fprintf(stderr, "[ERROR] %s\n", gx_last_error());

@@ -64,6 +64,11 @@ class CCompareCell(ctypes.Structure):
                 ("first_lcs", ctypes.c_uint64)]
 
 
+class CSuffixStats(ctypes.Structure):
+    _fields_ = [(k, ctypes.c_uint64) for k in ("num_internal", "num_leaves", "num_nodes", "string_depth_sum",
+                                               "max_string_depth", "longest_repeat_start", "longest_repeat_len")]
+
+
 class CResult(ctypes.Structure):
     _fields_ = [("score", ctypes.c_int64), ("matches", ctypes.c_uint64), ("mismatches", ctypes.c_uint64),
                 ("gap_extensions", ctypes.c_uint64), ("opening_gaps", ctypes.c_uint64),
@@ -88,7 +93,8 @@ EXPORTED = ["gx_last_error", "gx_version", "gx_context_create", "gx_context_dest
             "gx_config_load", "gx_format_alignment", "gx_format_table",
             "gx_common_substring_host", "gx_common_substring", "gx_compare_pair", "gx_compare_matrix",
             "gx_compare_info", "gx_compare_segment_height", "gx_compare_run_stats",
-            "gx_common_substring_candidates_host"]
+            "gx_common_substring_candidates_host",
+            "gx_suffix_tree_stats", "gx_suffix_info", "gx_suffix_tile", "gx_format_suffix_stats"]
 
 _lib = None
 
@@ -159,6 +165,11 @@ def lib():
     L.gx_compare_info.argtypes = [vp, u64p, u64p, u64p, u64p]
     L.gx_compare_segment_height.argtypes = []
     L.gx_compare_run_stats.argtypes = [vp, u64p, ctypes.POINTER(ctypes.c_double)]
+    dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
+    L.gx_suffix_tree_stats.argtypes = [vp, vp, sz, ctypes.POINTER(CSuffixStats), vp, vp, vp]
+    L.gx_suffix_info.argtypes = [vp, u64p, u64p, dp, dp, dp]
+    L.gx_suffix_tile.argtypes = [ip, ip, ip]
+    L.gx_format_suffix_stats.argtypes = [ctypes.POINTER(CSuffixStats), vp, sz, vp, sz, ctypes.POINTER(sz)]
     _lib = L
     return L
 
@@ -885,3 +896,128 @@ def compare_info(ctx: Optional["Context"] = None) -> dict:
 def compare_segment_height() -> int:
     """Rows per segment of the run kernel's tiles (gx_compare_segment_height)."""
     return lib().gx_compare_segment_height()
+
+
+# ---------------------------------------------------------------------------
+# suffix-tree mode (main.rs:154-215)
+
+@dataclass
+class TreeStats:
+    """TreeStats (tree.rs:30-39); string_depth_sum is the numerator of the average."""
+    num_internal: int = 0
+    num_leaves: int = 0
+    num_nodes: int = 0
+    average_string_depth: float = 0.0
+    max_string_depth: int = 0
+    bwt: str = ""
+    longest_repeat_len: int = 0
+    longest_repeat_start: int = 0
+    string_depth_sum: int = 0
+
+    def _c(self) -> CSuffixStats:
+        return CSuffixStats(self.num_internal, self.num_leaves, self.num_nodes, self.string_depth_sum,
+                            self.max_string_depth, self.longest_repeat_start, self.longest_repeat_len)
+
+    def __str__(self):  # display.rs:8-38
+        return format_suffix_stats(self._c(), self.bwt.encode("latin-1"))
+
+
+def format_suffix_stats(st: CSuffixStats, bwt: bytes) -> str:
+    """Display for TreeStats (gx_format_suffix_stats)."""
+    kb, pb = _buf(bwt)
+    need = ctypes.c_size_t()
+    rc = lib().gx_format_suffix_stats(ctypes.byref(st), pb, len(bwt), None, 0, ctypes.byref(need))
+    if rc not in (0, 7):
+        _check(rc)
+    out = ctypes.create_string_buffer(need.value)
+    _check(lib().gx_format_suffix_stats(ctypes.byref(st), pb, len(bwt), out, need.value, None))
+    return out.value.decode("latin-1")
+
+
+def suffix_tree_stats(seq: bytes, ctx: Optional["Context"] = None, want: Seq[str] = ("bwt",),
+                      host: bool = False) -> dict:
+    """compute_stats(0) on a tree holding seq (gx_suffix_tree_stats): a dict with "stats" (TreeStats,
+    its bwt filled when wanted), "raw" (CSuffixStats) and each of "bwt" (bytes), "sa", "lcp" (uint32
+    arrays of len(seq) + 1) named in `want`.  host=True: the host solver, no device."""
+    ptr = None if host else (ctx or default_context()).ptr
+    ks, ps = _buf(seq)
+    N = len(seq) + 1
+    arr = {k: np.zeros(N, np.uint8 if k == "bwt" else np.uint32) for k in ("bwt", "sa", "lcp") if k in want}
+    raw = CSuffixStats()
+    _check(lib().gx_suffix_tree_stats(ptr, ps, len(seq), ctypes.byref(raw),
+                                      *[arr[k].ctypes.data if k in arr else None for k in ("bwt", "sa", "lcp")]))
+    out = {"raw": raw}
+    if "bwt" in arr:
+        out["bwt"] = arr.pop("bwt").tobytes()
+    out.update(arr)
+    avg = raw.string_depth_sum / raw.num_internal if raw.num_internal else float("nan")   # 0 / 0 (tree.rs:801)
+    out["stats"] = TreeStats(raw.num_internal, raw.num_leaves, raw.num_nodes, avg, raw.max_string_depth,
+                             out.get("bwt", b"").decode("latin-1"), raw.longest_repeat_len,
+                             raw.longest_repeat_start, raw.string_depth_sum)
+    return out
+
+
+def suffix_info(ctx: Optional["Context"] = None) -> dict:
+    """gx_suffix_info of the last suffix-tree call on ctx (all zero: the host solver answered)."""
+    ctx = ctx or default_context()
+    r, p = ctypes.c_uint64(), ctypes.c_uint64()
+    ms = [ctypes.c_double() for _ in range(3)]
+    _check(lib().gx_suffix_info(ctx.ptr, ctypes.byref(r), ctypes.byref(p), *[ctypes.byref(x) for x in ms]))
+    return {"doubling_rounds": r.value, "sort_passes": p.value, "sort_ms": ms[0].value, "lcp_ms": ms[1].value,
+            "fold_ms": ms[2].value}
+
+
+def suffix_tile() -> Tuple[int, int, int]:
+    """(T, C, B) of gx_suffix_tile: sort items per workgroup, LCP chunk, fold block."""
+    v = [ctypes.c_int() for _ in range(3)]
+    _check(lib().gx_suffix_tile(*[ctypes.byref(x) for x in v]))
+    return v[0].value, v[1].value, v[2].value
+
+
+# STRING_TERMINATORS (tree.rs:66-69)
+_TERMINATORS = "$!@#%^&*()-_=+{}[]|;:'<>,.?/~` \n"
+
+
+class SuffixTree:
+    """The crate-shaped suffixtree::tree::SuffixTree (tree.rs:41-190) without the tree: compute_stats
+    reads the suffix array, get_lcs is compare mode's common_substring.  Graphviz
+    output and suffix links are out of scope (suffix_links is accepted and ignored).
+    host=True keeps every call on the host solvers (no device)."""
+
+    def __init__(self, alphabet_file: str, initial_allocation: int = 0, ctx: Optional["Context"] = None,
+                 host: bool = False):
+        try:
+            with open(alphabet_file, "r") as f:
+                alphabet = f.read().replace(" ", "")
+        except OSError:
+            raise RuntimeError(f"Could not read alphabet file: {alphabet_file}")   # tree.rs:143
+        self.alphabet = sorted(list(_TERMINATORS) + list(alphabet))
+        self.strings: List[str] = []
+        self.stats = TreeStats()
+        self._ctx = ctx
+        self._host = host
+
+    def insert_string(self, new_string: str, enable_suffix_links: bool = False, print_time: bool = False) -> None:
+        if len(self.strings) >= len(_TERMINATORS):
+            raise IndexError("the suffix tree can support up to 32 strings")   # tree.rs:65
+        for c in new_string:
+            if c not in self.alphabet:
+                raise ValueError(f"Character {c} not found in alphabet")   # tree.rs:56-63
+        self.strings.append(new_string + _TERMINATORS[len(self.strings)])
+
+    def _bare(self, idx: int) -> bytes:
+        return self.strings[idx][:-1].encode("latin-1")
+
+    def compute_stats(self, string_idx: int = 0) -> None:
+        if string_idx != 0:
+            raise NotImplementedError("compute_stats: only string 0 (the reference's leaf-id test holds for it alone)")
+        r = suffix_tree_stats(self._bare(0), ctx=self._ctx, want=("bwt",), host=self._host)
+        self.stats = r["stats"]
+
+    def get_lcs(self, string_one_idx: int, string_two_idx: int) -> Tuple[int, int, int]:
+        """get_lcs (tree.rs:218-281): (i, j, length)."""
+        a, b = self._bare(string_one_idx), self._bare(string_two_idx)
+        return common_substring_host(a, b) if self._host else common_substring(a, b, self._ctx)
+
+    def __str__(self):  # display.rs:40-56 without the Graphviz block
+        return f"\nStats: {self.stats}\n"

@@ -378,6 +378,47 @@ int gx_compare_run_stats(const gx_context* ctx, uint64_t* byte_compares, double*
 int gx_common_substring_candidates_host(const uint8_t* a, size_t n, const uint8_t* b, size_t m,
                                         uint64_t* len, uint64_t* n_candidates);
 
+/* ---- suffix-tree mode (main.rs:154-215) ----------------------------------
+ * What compute_stats (tree.rs:740-803) reads off the suffix tree of
+ * t = s + '$' is a function of the suffix array SA and the LCP array of t
+ * (suffixes in plain byte order, LCP[0] = 0), which the GPU builds with radix
+ * sorts and scans instead of a tree.  Input bytes must be above
+ * '$' (0x24) -> GX_EINVAL otherwise; n >= 2^30 -> GX_ERANGE.  N = n + 1. */
+
+/* TreeStats (tree.rs:30-39) without the BWT; average_string_depth =
+ * string_depth_sum / num_internal as f64 (NaN for 0 / 0).  num_internal counts
+ * the non-root internal nodes, num_nodes = num_internal + num_leaves + 1,
+ * longest_repeat_start is the reference's 1-based leaf id (0: no repeat). */
+typedef struct gx_suffix_stats {
+    uint64_t num_internal, num_leaves, num_nodes, string_depth_sum,
+             max_string_depth, longest_repeat_start, longest_repeat_len;
+} gx_suffix_stats;
+/* compute_stats(0) on a tree holding s.  bwt (n+1 bytes), sa, lcp (n+1 uint32
+ * each) may be NULL.  ctx = NULL: host solver, no device.  With a context,
+ * inputs shorter than GX_SUFFIX_HOST_BELOW bytes (default 4096, the lower
+ * bracket of the measured crossing: DESIGN.md 17.3) and the empty input go to
+ * the host solver too.  When the doubling's bound on max LCP puts the LCP
+ * kernel's work, (N / C) * max LCP / 8 eight-byte compares, above
+ * GX_SUFFIX_LCP_BUDGET (default 2^40: unary or long-period input of tens of Mi
+ * bases), the LCP array and the statistics are finished on the host from the
+ * device's suffix array. */
+int gx_suffix_tree_stats(gx_context* ctx, const uint8_t* s, size_t n, gx_suffix_stats* out,
+                         uint8_t* bwt, uint32_t* sa, uint32_t* lcp);
+/* The last suffix-tree call on ctx: sorts (prefix-doubling rounds, the first
+ * included), radix passes that ran, and the device time (ms) of the sorts, the
+ * LCP kernel and the statistics fold.  All zero when the host solver answered.
+ * Measurement only. */
+int gx_suffix_info(const gx_context* ctx, uint64_t* doubling_rounds, uint64_t* sort_passes,
+                   double* sort_ms, double* lcp_ms, double* fold_ms);
+/* Items per workgroup of the sort and scan kernels, text positions per lane of
+ * the LCP kernel, LCP entries per block of the fold.  Tests only. */
+int gx_suffix_tile(int* sort_items_per_wg, int* lcp_chunk, int* fold_block);
+/* Display for TreeStats (display.rs:8-38) byte for byte: leading newline,
+ * 12-space indentation, the BWT cut to 100 bytes with "... (truncated)".
+ * GX_ECAP reports *needed (with the terminating NUL). */
+int gx_format_suffix_stats(const gx_suffix_stats* st, const uint8_t* bwt, size_t bwt_len,
+                           char* out, size_t cap, size_t* needed);
+
 #ifdef __cplusplus
 }
 #endif
