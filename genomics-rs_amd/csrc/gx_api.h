@@ -326,6 +326,7 @@ struct gx_context {
     double cmp_run_ms = 0.0;     // ... and their device time
     // the last suffix-tree call (gx_suffix_info; gx_api_suffix.cpp)
     uint64_t suf_rounds = 0, suf_passes = 0;
+    uint64_t suf_digit_passes[8] = {};
     double suf_sort_ms = 0.0, suf_lcp_ms = 0.0, suf_fold_ms = 0.0;
 };
 

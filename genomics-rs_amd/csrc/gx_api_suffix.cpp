@@ -126,6 +126,7 @@ constexpr uint64_t kSuffixLcpBudgetDefault = 1ull << 40;
 
 struct SufInfo {
     uint64_t rounds = 0, passes = 0;
+    uint64_t digit_passes[8] = {};   // passes per digit byte (bits 8p .. 8p+7), over all rounds, round 0 included
     double sort_ms = 0, lcp_ms = 0, fold_ms = 0;
 };
 
@@ -201,6 +202,7 @@ int suffix_device(gx_context* ctx, const uint8_t* t, uint32_t N, gx_suffix_stats
                                          (uint32_t*)d_tmp.p, st));
             cur ^= 1;
             ++info.passes;
+            ++info.digit_passes[p];
         }
         SUF_TRY(hipEventRecord(ctx->ev1, st));
         SUF_TRY(launch_suf_ranks(K(cur), V(cur), N, flags, (uint32_t*)d_tmp.p, rank, d_last, st));
@@ -313,6 +315,7 @@ extern "C" int gx_suffix_tree_stats(gx_context* ctx, const uint8_t* s, size_t n,
     // (a call answered by the host solver leaves zeros: no kernel ran)
     ctx->suf_rounds = info.rounds;
     ctx->suf_passes = info.passes;
+    for (int p = 0; p < 8; ++p) ctx->suf_digit_passes[p] = info.digit_passes[p];
     ctx->suf_sort_ms = info.sort_ms;
     ctx->suf_lcp_ms = info.lcp_ms;
     ctx->suf_fold_ms = info.fold_ms;
@@ -327,6 +330,12 @@ extern "C" int gx_suffix_info(const gx_context* ctx, uint64_t* doubling_rounds, 
     if (sort_ms) *sort_ms = ctx->suf_sort_ms;
     if (lcp_ms) *lcp_ms = ctx->suf_lcp_ms;
     if (fold_ms) *fold_ms = ctx->suf_fold_ms;
+    return GX_OK;
+}
+
+extern "C" int gx_suffix_digit_passes(const gx_context* ctx, uint64_t passes[8]) {
+    if (!ctx || !passes) return fail(GX_EINVAL, "NULL argument");
+    for (int p = 0; p < 8; ++p) passes[p] = ctx->suf_digit_passes[p];
     return GX_OK;
 }
 

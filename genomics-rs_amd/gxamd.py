@@ -94,7 +94,7 @@ EXPORTED = ["gx_last_error", "gx_version", "gx_context_create", "gx_context_dest
             "gx_common_substring_host", "gx_common_substring", "gx_compare_pair", "gx_compare_matrix",
             "gx_compare_info", "gx_compare_segment_height", "gx_compare_run_stats",
             "gx_common_substring_candidates_host",
-            "gx_suffix_tree_stats", "gx_suffix_info", "gx_suffix_tile", "gx_format_suffix_stats"]
+            "gx_suffix_tree_stats", "gx_suffix_info", "gx_suffix_digit_passes", "gx_suffix_tile", "gx_format_suffix_stats"]
 
 _lib = None
 
@@ -168,6 +168,7 @@ def lib():
     dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
     L.gx_suffix_tree_stats.argtypes = [vp, vp, sz, ctypes.POINTER(CSuffixStats), vp, vp, vp]
     L.gx_suffix_info.argtypes = [vp, u64p, u64p, dp, dp, dp]
+    L.gx_suffix_digit_passes.argtypes = [vp, u64p]
     L.gx_suffix_tile.argtypes = [ip, ip, ip]
     L.gx_format_suffix_stats.argtypes = [ctypes.POINTER(CSuffixStats), vp, sz, vp, sz, ctypes.POINTER(sz)]
     _lib = L
@@ -958,13 +959,17 @@ def suffix_tree_stats(seq: bytes, ctx: Optional["Context"] = None, want: Seq[str
 
 
 def suffix_info(ctx: Optional["Context"] = None) -> dict:
-    """gx_suffix_info of the last suffix-tree call on ctx (all zero: the host solver answered)."""
+    """gx_suffix_info of the last suffix-tree call on ctx (all zero: the host solver answered), and
+    "digit_passes": the radix passes on key bits 8p .. 8p+7 for p = 0 .. 7, round 0 (text keys, as a rule
+    one pass on every digit) included (gx_suffix_digit_passes)."""
     ctx = ctx or default_context()
     r, p = ctypes.c_uint64(), ctypes.c_uint64()
     ms = [ctypes.c_double() for _ in range(3)]
     _check(lib().gx_suffix_info(ctx.ptr, ctypes.byref(r), ctypes.byref(p), *[ctypes.byref(x) for x in ms]))
+    digits = (ctypes.c_uint64 * 8)()
+    _check(lib().gx_suffix_digit_passes(ctx.ptr, digits))
     return {"doubling_rounds": r.value, "sort_passes": p.value, "sort_ms": ms[0].value, "lcp_ms": ms[1].value,
-            "fold_ms": ms[2].value}
+            "fold_ms": ms[2].value, "digit_passes": list(digits)}
 
 
 def suffix_tile() -> Tuple[int, int, int]:

@@ -410,6 +410,15 @@ int gx_suffix_tree_stats(gx_context* ctx, const uint8_t* s, size_t n, gx_suffix_
  * Measurement only. */
 int gx_suffix_info(const gx_context* ctx, uint64_t* doubling_rounds, uint64_t* sort_passes,
                    double* sort_ms, double* lcp_ms, double* fold_ms);
+/* The radix passes of the last suffix-tree call on ctx by digit: passes[p] =
+ * the passes that sorted on key bits 8p .. 8p+7, over all rounds, round 0
+ * included (their sum is sort_passes).  A digit that is the same in every key
+ * of a round is skipped there.  Round 0's keys are text bytes and as a rule
+ * differ in all eight digits, so it adds one to every entry; from round 1 on
+ * the keys are rank pairs, p = 0..3 the low rank and p = 4..7 the high one, so
+ * a pass on rank bits 16-23 shows as passes[2], passes[6] >= 2.  All zero
+ * when the host solver answered.  Measurement and tests. */
+int gx_suffix_digit_passes(const gx_context* ctx, uint64_t passes[8]);
 /* Items per workgroup of the sort and scan kernels, text positions per lane of
  * the LCP kernel, LCP entries per block of the fold.  Tests only. */
 int gx_suffix_tile(int* sort_items_per_wg, int* lcp_chunk, int* fold_block);

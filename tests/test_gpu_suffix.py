@@ -3,7 +3,30 @@ gx_suffix_tree_stats element by element against the host solver (itself pinned
 by tests/test_suffix_host.py), at the sizes where the kernels of gx_suffix.hip
 change path (T sort items per workgroup, C text positions per LCP lane, B LCP
 entries per fold block), on the reference's fixtures, and through `gx-align
-suffix-tree`."""
+suffix-tree`.
+
+The host solver and the device share their construction (the doubling's keys,
+the zero padding, Kasai's order), so the second family of tests here does not
+consult it: check_definition verifies the device's own arrays from the
+definitions (tests/suffix_check.py).  Its sizes, with W = 256 threads per
+workgroup, N = n + 1:
+
+  rank scan's chunk edge    N in {W T, W T + 1}: 256 and 257 partials of the
+                            scan over the head flags, where the one-workgroup
+                            scan of the partials starts to carry between chunks
+  table scan's chunk edge   N in {T T, T T + 1}: T and T + 1 tiles, 256 and 257
+                            partials of the scan over the [256][tiles] histogram
+                            table of every radix pass (the largest cases here)
+  every admitted byte       0x25..0xFF at n = T - 1 and 5,000, {0x7F, 0x80} at
+                            5,000: keys with bit 63 set, digits above 'T'
+  many rounds, wide ranks   48 mutated copies of a 4,096-base block, N = 196,609:
+                            seven doubling rounds or more and radix passes on
+                            rank bits 16-23 (beyond round 0's one per digit)
+  NULL outputs              every subset of one of (bwt, sa, lcp), and none
+  sizes falling and rising  n = 4 T + 1, 65, 3 T, 1, 4 T + 1 on one context: the
+                            pooled buffers larger than the call and stale
+
+Not covered: N >= 2^24, the fourth digit byte of a rank."""
 import json
 import os
 import random
@@ -14,7 +37,9 @@ import numpy as np
 import pytest
 
 from conftest import GOLDEN, ROOT
-from test_suffix_host import load_vectors, raw_dict, read_bwt_file, read_golden, vector_text
+from suffix_check import check_arrays, fold_stats
+from test_suffix_host import (BYTES_219, SIGN_EDGE, load_vectors, mutated_tandem_copies, np_rand, raw_dict,
+                              read_bwt_file, read_golden, vector_text)
 
 pytestmark = pytest.mark.gpu
 
@@ -42,6 +67,34 @@ def check(gx, ctx, s: bytes):
     assert raw_dict(d["raw"]) == raw_dict(h["raw"])
     assert info["doubling_rounds"] >= 1 and info["sort_passes"] >= 1, info
     return d, info
+
+
+def check_definition(gx, ctx, s: bytes, want=WANT, max_work=None):
+    """The device's own SA, LCP and BWT satisfy their definitions and its
+    statistics are their fold (tests/suffix_check.py), and the kernels ran,
+    the LCP and fold kernels included.  The host solver is not consulted.
+    `want` must name sa and lcp (there is nothing to check without them); bwt
+    is checked when it is asked for."""
+    assert "sa" in want and "lcp" in want, want
+    d = gx.suffix_tree_stats(s, ctx=ctx, want=want)
+    info = gx.suffix_info(ctx)
+    assert info["doubling_rounds"] >= 1 and info["sort_passes"] >= 1, info
+    assert info["lcp_ms"] > 0 and info["fold_ms"] > 0, info
+    assert sum(info["digit_passes"]) == info["sort_passes"], info
+    check_arrays(s, d["sa"], d["lcp"], d.get("bwt"), max_work=max_work)
+    assert raw_dict(d["raw"]) == fold_stats(d["sa"], d["lcp"])
+    return d, info
+
+
+def scan_chunk(gx):
+    """(T, W): sort and scan items per workgroup, and the partials the
+    one-workgroup scan of suf_scan_part_kernel takes per chunk, which is the
+    workgroup size kSufBlock.  gx_suffix_tile does not report kSufBlock itself;
+    the fold block B is defined as kSufBlock (kSufFoldBlock = kSufBlock,
+    gx_suffix.h), so B stands in for it and is pinned to the literal here."""
+    T, _, B = tiles(gx)
+    assert B == 256
+    return T, 256
 
 
 def rand(rng, alpha: bytes, n: int) -> bytes:
@@ -131,6 +184,77 @@ def test_lcp_budget_finishes_on_host(gx, ctx, monkeypatch):
     _, info = check(gx, ctx, s)
     assert info["lcp_ms"] == 0 and info["fold_ms"] == 0 and info["sort_passes"] >= 1, info
     check(gx, ctx, rand(random.Random(3), b"ACGT", 5000))
+
+
+def test_rank_scan_chunk_edge(gx, ctx):
+    """256 and 257 partials in the scan of the head flags: without the carry
+    between chunks of suf_scan_part_kernel the ranks restart in the last tile."""
+    T, W = scan_chunk(gx)
+    for N in (W * T, W * T + 1):
+        assert -(-N // T) == W + (N > W * T)
+        check_definition(gx, ctx, np_rand(N, b"ACGT", N - 1))
+
+
+@pytest.mark.parametrize("extra", [0, 1], ids=["tiles_T", "tiles_T_plus_1"])
+def test_table_scan_chunk_edge(gx, ctx, extra):
+    """T and T + 1 tiles: the [256][tiles] histogram table of a radix pass has
+    256 T and 256 (T + 1) entries, 256 and 257 partials of its scan."""
+    T, W = scan_chunk(gx)
+    N = T * T + extra
+    tiles_n = -(-N // T)
+    assert tiles_n == T + extra and -(-256 * tiles_n // T) == W + extra
+    check_definition(gx, ctx, np_rand(N, b"ACGT", N - 1))
+
+
+@pytest.mark.parametrize("alpha, n", [(BYTES_219, None), (BYTES_219, 5000), (SIGN_EDGE, 5000)],
+                         ids=["bytes219_T-1", "bytes219_5000", "7f80_5000"])
+def test_full_byte_range(gx, ctx, alpha, n):
+    """Every byte the ABI admits: round 0 keys with bit 63 set, radix digits up to 0xFF."""
+    T, _, _ = tiles(gx)
+    s = np_rand(len(alpha), alpha, T - 1 if n is None else n)
+    check(gx, ctx, s)
+    check_definition(gx, ctx, s)
+
+
+def test_many_rounds_wide_ranks(gx, ctx):
+    """digit_passes counts round 0 as well, whose keys are 8 text bytes and differ
+    in every digit byte: round 0 gives exactly one pass per digit, whatever N.
+    So a pass on rank bits 16-23 shows as a count of two or more in digits 2
+    and 6 (the low and the high half of a rank pair), never as one.  The
+    control is a short input, whose ranks fit two digit bytes; and here
+    N < 2^24, so digits 3 and 7 stay at round 0's one."""
+    _, small = check_definition(gx, ctx, np_rand(12, b"ACGT", 5000))
+    assert small["doubling_rounds"] >= 2, small
+    assert [small["digit_passes"][p] for p in (2, 3, 6, 7)] == [1, 1, 1, 1], small
+    s = mutated_tandem_copies()
+    assert 1 << 16 < len(s) + 1 == 196609 < 1 << 24
+    d, info = check_definition(gx, ctx, s)
+    assert info["doubling_rounds"] >= 7, info
+    assert info["digit_passes"][2] >= 2 and info["digit_passes"][6] >= 2, info
+    assert info["digit_passes"][3] == 1 and info["digit_passes"][7] == 1, info
+
+
+def test_null_outputs(gx, ctx):
+    """Any of bwt, sa, lcp may be NULL: the statistics and the other arrays do not change."""
+    s = np_rand(11, b"ACGT", 5000)
+    full, _ = check_definition(gx, ctx, s)
+    stats = fold_stats(full["sa"], full["lcp"])
+    for want in ((), ("sa",), ("lcp",), ("bwt",), WANT):
+        d = gx.suffix_tree_stats(s, ctx=ctx, want=want)
+        info = gx.suffix_info(ctx)
+        assert info["sort_passes"] >= 1 and info["lcp_ms"] > 0 and info["fold_ms"] > 0, (want, info)
+        assert raw_dict(d["raw"]) == stats, want
+        assert sorted(k for k in d if k in WANT) == sorted(want)
+        for k in want:
+            assert np.array_equal(d[k], full[k]) if k != "bwt" else d[k] == full[k], (want, k)
+
+
+def test_sizes_falling_and_rising(gx, ctx):
+    """One context, sizes down and up again: the pooled table, scan and flag
+    buffers are larger than the call needs and hold the previous call's data."""
+    T, _, _ = tiles(gx)
+    for k, n in enumerate((4 * T + 1, 65, 3 * T, 1, 4 * T + 1)):
+        check_definition(gx, ctx, np_rand(100 + k, b"ACGT", n))
 
 
 def test_empty_input_with_context(gx, ctx):

@@ -2,7 +2,11 @@
 ctx = NULL against a brute-force restatement (suffixes sorted explicitly, LCP by
 direct compare, the interval rule of DESIGN.md 17.1), against the reference's
 own BWT files and asserted node counts (tests/golden/suffix), the error codes,
-Display for TreeStats, and the crate-shaped SuffixTree mirror."""
+Display for TreeStats, and the crate-shaped SuffixTree mirror.  Beyond the
+brute force's reach (n > 300: every admitted byte, half a Mi of random ACGT,
+mutated tandem copies, unary input) the checker of tests/suffix_check.py is
+the reference; it is itself checked against the brute force and against seven
+corruptions it must reject."""
 import gzip
 import hashlib
 import json
@@ -15,6 +19,7 @@ import pytest
 
 import oracle as oracle_mod
 from conftest import COMPARISON, GOLDEN, read_fasta_records
+from suffix_check import check_arrays, fold_stats
 
 SUFFIX = os.path.join(GOLDEN, "suffix")
 ALPHABETS = os.path.join(GOLDEN, "alphabets")
@@ -84,6 +89,7 @@ def raw_dict(raw):
 
 
 def test_host_matches_brute_force(gx):
+    # (brute_cases() below restates this generator: seed, lengths, alphabets; keep the two in step)
     rng = random.Random(20260117)
     lengths = [0, 1, 2, 3, 7, 8, 9, 15, 16, 17, 300] + [rng.randrange(0, 301) for _ in range(189)]
     assert len(lengths) == 200
@@ -211,6 +217,146 @@ def test_suffix_tree_mirror_get_lcs(gx):
         assert got == gx.common_substring_host(a.encode(), b.encode())
         if expect:
             assert got == expect, c["name"]
+
+
+# ---------------------------------------------------------------------------
+# Beyond brute's reach the reference is tests/suffix_check.py: check_arrays and
+# fold_stats verify the arrays from the definitions and share nothing with the
+# host solver's construction (doubling, its keys and padding, Kasai's order).
+
+BYTES_219 = bytes(range(0x25, 0x100))   # every byte the ABI admits
+SIGN_EDGE = b"\x7f\x80"                 # straddles the sign bit of a byte
+
+
+def np_rand(seed, alpha: bytes, n: int) -> bytes:
+    """n letters of alpha, uniform, from numpy.random.default_rng(seed)."""
+    letters = np.frombuffer(alpha, np.uint8)
+    return letters[np.random.default_rng(seed).integers(0, len(alpha), n)].tobytes()
+
+
+def mutated_tandem_copies(seed=7, copies=48, block=4096, mutations=64) -> bytes:
+    """`copies` copies of one random ACGT block, each with `mutations` positions
+    (drawn without replacement) overwritten with random letters: long repeats
+    between every pair of copies, so many doubling rounds, at a length whose
+    ranks need three digit bytes (48 * 4,096 + 1 = 196,609 suffixes)."""
+    rng = np.random.default_rng(seed)
+    letters = np.frombuffer(b"ACGT", np.uint8)
+    text = np.tile(letters[rng.integers(0, 4, block)], (copies, 1))
+    for c in range(copies):
+        text[c, rng.choice(block, mutations, replace=False)] = letters[rng.integers(0, 4, mutations)]
+    return text.tobytes()
+
+
+def brute_cases():
+    """The 200 strings of test_host_matches_brute_force, by a copy of its
+    generator (that test is left as it was): the same seed, lengths and
+    alphabet rotation, drawn in the same order.  Keep the two in step."""
+    rng = random.Random(20260117)
+    lengths = [0, 1, 2, 3, 7, 8, 9, 15, 16, 17, 300] + [rng.randrange(0, 301) for _ in range(189)]
+    for k, n in enumerate(lengths):
+        alpha = (b"A", b"AC", b"ACGT")[k % 3]
+        yield bytes(rng.choice(alpha) for _ in range(n))
+
+
+def test_checker_accepts_brute_force():
+    cases = list(brute_cases())
+    assert len(cases) == 200
+    for s in cases:
+        sa, lcp, bwt, st = brute(s)
+        assert check_arrays(s, sa, lcp, bwt, max_work=len(s) ** 2 + 1) == sum(lcp) + len(s), s
+        assert fold_stats(sa, lcp) == st, s
+
+
+@pytest.fixture(scope="module")
+def solved_3000(gx):
+    s = np_rand(3000, b"ACGT", 3000)
+    r = gx.suffix_tree_stats(s, host=True, want=("bwt", "sa", "lcp"))
+    check_arrays(s, r["sa"], r["lcp"], r["bwt"])
+    return s, r["sa"], r["lcp"], np.frombuffer(r["bwt"], np.uint8)
+
+
+def corrupt_lcp_plus_one(s, sa, lcp, bwt):
+    lcp[1500] += 1
+
+
+def corrupt_lcp_max_minus_one(s, sa, lcp, bwt):
+    lcp[np.argmax(lcp)] -= 1
+
+
+def corrupt_sa_swap(s, sa, lcp, bwt):
+    sa[[1500, 1501]] = sa[[1501, 1500]]
+
+
+def corrupt_sa_duplicate(s, sa, lcp, bwt):
+    sa[1500] = sa[700]
+
+
+def corrupt_bwt_byte(s, sa, lcp, bwt):
+    bwt[1500] = ord("A") if bwt[1500] != ord("A") else ord("C")
+
+
+def corrupt_lcp0(s, sa, lcp, bwt):
+    lcp[0] = 1
+
+
+@pytest.mark.parametrize("corrupt, clause", [
+    (corrupt_lcp_plus_one, "bounds|too large"), (corrupt_lcp_max_minus_one, "order"), (corrupt_sa_swap, None),
+    (corrupt_sa_duplicate, "permutation"), (corrupt_bwt_byte, "bwt"), (corrupt_lcp0, r"lcp\[0\]")],
+    ids=lambda v: v.__name__[8:] if callable(v) else None)
+def test_checker_rejects_corruption(solved_3000, corrupt, clause):
+    s, sa, lcp, bwt = solved_3000
+    sa, lcp, bwt = sa.copy(), lcp.copy(), bwt.copy()
+    corrupt(s, sa, lcp, bwt)
+    with pytest.raises(AssertionError, match=clause):
+        check_arrays(s, sa, lcp, bwt)
+
+
+def test_checker_work_cap_fails(solved_3000):
+    s, sa, lcp, bwt = solved_3000
+    total = int(lcp.sum())
+    assert check_arrays(s, sa, lcp, bwt, max_work=total) == total + len(s)
+    with pytest.raises(AssertionError, match="max_work"):
+        check_arrays(s, sa, lcp, bwt, max_work=total - 1)
+    # the default cap, 128 * N, on an input far above it
+    u = b"A" * 1000
+    usa, ulcp, ubwt, _ = brute(u)
+    with pytest.raises(AssertionError, match="max_work"):
+        check_arrays(u, usa, ulcp, ubwt)
+
+
+def host_against_checker(gx, s, max_work=None):
+    r = gx.suffix_tree_stats(s, host=True, want=("bwt", "sa", "lcp"))
+    check_arrays(s, r["sa"], r["lcp"], r["bwt"], max_work=max_work)
+    assert raw_dict(r["raw"]) == fold_stats(r["sa"], r["lcp"])
+    return r
+
+
+def test_host_full_byte_range(gx):
+    """Bytes up to 0xFF: round 0 keys with bit 63 set, and the unsigned order at the sign bit."""
+    for alpha in (BYTES_219, SIGN_EDGE):
+        s = np_rand(len(alpha), alpha, 300)
+        r = gx.suffix_tree_stats(s, host=True, want=("bwt", "sa", "lcp"))
+        sa, lcp, bwt, st = brute(s)   # (Python compares bytes unsigned)
+        assert (r["sa"].tolist(), r["lcp"].tolist(), r["bwt"], raw_dict(r["raw"])) == (sa, lcp, bwt, st)
+    host_against_checker(gx, np_rand(219, BYTES_219, 5000))
+    host_against_checker(gx, np_rand(2, SIGN_EDGE, 5000))
+
+
+def test_host_random_half_mi(gx):
+    host_against_checker(gx, np_rand(524288, b"ACGT", 524288))
+
+
+def test_host_mutated_tandem_copies(gx):
+    s = mutated_tandem_copies()
+    assert len(s) + 1 == 196609
+    r = host_against_checker(gx, s)   # (inside the default cap: sum(lcp) / N is near 80)
+    assert r["raw"].max_string_depth >= 256   # more than the offsets 8 .. 128 resolve: eight rounds or more
+
+
+def test_host_unary_threshold(gx):
+    s = b"A" * 4096
+    r = host_against_checker(gx, s, max_work=(len(s) + 1) ** 2)
+    assert r["raw"].max_string_depth == 4095
 
 
 def test_tile_constants(gx):
