@@ -322,6 +322,7 @@ struct gx_context {
     Scores32 kept_sc{};
     // the last compare call (gx_compare_info, gx_compare_run_stats; gx_api_compare.cpp)
     uint64_t cmp_gpu = 0, cmp_host = 0, cmp_ovf = 0, cmp_levels = 0;
+    uint64_t cmp_batches = 0;    // gpu_batch calls (gx_compare_batches)
     uint64_t cmp_cells = 0;      // byte compares of its run-kernel launches
     double cmp_run_ms = 0.0;     // ... and their device time
     // the last suffix-tree call (gx_suffix_info; gx_api_suffix.cpp)

@@ -165,7 +165,7 @@ struct Cmp {
     int H = kLcsubSeg;
     bool recurse = true;
     std::vector<PairAcc> acc;
-    uint64_t n_gpu = 0, n_host = 0, n_ovf = 0, levels = 0, cells = 0;
+    uint64_t n_gpu = 0, n_host = 0, n_ovf = 0, levels = 0, batches = 0, cells = 0;
     double run_ms = 0.0;
 };
 
@@ -202,6 +202,7 @@ void host_subtree(Cmp& c, const Sub& s0) {
 int gpu_batch(Cmp& c, const Sub* subs, size_t nsub, std::vector<Sub>& next) {
     gx_context* ctx = c.ctx;
     hipStream_t st = ctx->stream;
+    ++c.batches;
     std::vector<LcsubDesc> desc(nsub);
     uint64_t elems = 0, tiles = 0, dtiles = 0, cells = 0;
     for (size_t k = 0; k < nsub; ++k) {
@@ -414,6 +415,7 @@ int compare_core(gx_context* ctx, const uint8_t* const* seqs, const size_t* lens
     ctx->cmp_host = c.n_host;
     ctx->cmp_ovf = c.n_ovf;
     ctx->cmp_levels = c.levels;
+    ctx->cmp_batches = c.batches;
     ctx->cmp_cells = c.cells;
     ctx->cmp_run_ms = c.run_ms;
     return rc;
@@ -501,6 +503,12 @@ extern "C" int gx_compare_info(const gx_context* ctx, uint64_t* gpu_subproblems,
     if (host_subproblems) *host_subproblems = ctx->cmp_host;
     if (overflowed) *overflowed = ctx->cmp_ovf;
     if (levels) *levels = ctx->cmp_levels;
+    return GX_OK;
+}
+
+extern "C" int gx_compare_batches(const gx_context* ctx, uint64_t* batches) {
+    if (!ctx) return fail(GX_EINVAL, "ctx is NULL");
+    if (batches) *batches = ctx->cmp_batches;
     return GX_OK;
 }
 

@@ -92,7 +92,7 @@ EXPORTED = ["gx_last_error", "gx_version", "gx_context_create", "gx_context_dest
             "gx_fasta_load",
             "gx_config_load", "gx_format_alignment", "gx_format_table",
             "gx_common_substring_host", "gx_common_substring", "gx_compare_pair", "gx_compare_matrix",
-            "gx_compare_info", "gx_compare_segment_height", "gx_compare_run_stats",
+            "gx_compare_info", "gx_compare_batches", "gx_compare_segment_height", "gx_compare_run_stats",
             "gx_common_substring_candidates_host",
             "gx_suffix_tree_stats", "gx_suffix_info", "gx_suffix_digit_passes", "gx_suffix_tile", "gx_format_suffix_stats"]
 
@@ -163,6 +163,7 @@ def lib():
     L.gx_compare_pair.argtypes = [vp, vp, sz, vp, sz, ctypes.POINTER(CCompareCell), u64p]
     L.gx_compare_matrix.argtypes = [vp, vp, vp, sz, vp]
     L.gx_compare_info.argtypes = [vp, u64p, u64p, u64p, u64p]
+    L.gx_compare_batches.argtypes = [vp, u64p]
     L.gx_compare_segment_height.argtypes = []
     L.gx_compare_run_stats.argtypes = [vp, u64p, ctypes.POINTER(ctypes.c_double)]
     dp, ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_int)
@@ -884,14 +885,15 @@ def compare_matrix(seqs: Seq[bytes], ctx: Optional["Context"] = None, host: bool
 
 
 def compare_info(ctx: Optional["Context"] = None) -> dict:
-    """gx_compare_info / gx_compare_run_stats of the last compare call on ctx."""
+    """gx_compare_info / gx_compare_batches / gx_compare_run_stats of the last compare call on ctx."""
     ctx = ctx or default_context()
-    v = [ctypes.c_uint64() for _ in range(5)]
+    v = [ctypes.c_uint64() for _ in range(6)]
     ms = ctypes.c_double()
     _check(lib().gx_compare_info(ctx.ptr, *[ctypes.byref(x) for x in v[:4]]))
     _check(lib().gx_compare_run_stats(ctx.ptr, ctypes.byref(v[4]), ctypes.byref(ms)))
+    _check(lib().gx_compare_batches(ctx.ptr, ctypes.byref(v[5])))
     return {"gpu_subproblems": v[0].value, "host_subproblems": v[1].value, "overflowed": v[2].value,
-            "levels": v[3].value, "byte_compares": v[4].value, "run_ms": ms.value}
+            "levels": v[3].value, "batches": v[5].value, "byte_compares": v[4].value, "run_ms": ms.value}
 
 
 def compare_segment_height() -> int:

@@ -366,6 +366,11 @@ int gx_compare_matrix(gx_context* ctx, const uint8_t* const* seqs, const size_t*
  * counterpart (measurement only). */
 int gx_compare_info(const gx_context* ctx, uint64_t* gpu_subproblems, uint64_t* host_subproblems,
                     uint64_t* overflowed, uint64_t* levels);
+/* Batches of launches (run, combine, candidate) of the last compare call on
+ * ctx: one per level, more where a level's sub-problems exceed the budget of
+ * tile elements or of candidate slots of one batch.  Measurement and tests
+ * only. */
+int gx_compare_batches(const gx_context* ctx, uint64_t* batches);
 /* Rows per segment of the run kernel's tiles: diagonals are
  * cut every this many rows of a.  Measurement and tests only. */
 int gx_compare_segment_height(void);

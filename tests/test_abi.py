@@ -22,7 +22,8 @@ def declared_symbols():
 def test_header_declares_api():
     syms = declared_symbols()
     for s in ("gx_alignment_table", "gx_retrace", "gx_align", "gx_align_batch", "gx_table_export",
-              "gx_fasta_load", "gx_config_load", "gx_last_error"):
+              "gx_fasta_load", "gx_config_load", "gx_last_error",
+              "gx_compare_batches"):
         assert s in syms
 
 

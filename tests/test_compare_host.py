@@ -11,7 +11,11 @@ contract in DESIGN.md 16.1:
 The restatement builds the O(n m) table of diagonal run lengths with numpy and
 sorts the candidate substrings and terminated suffixes explicitly.  It is
 pinned by the reference's own get_lcs assertions (tests/golden/
-lcs_vectors.json, from tests/test_suffixtree.rs:135-237)."""
+lcs_vectors.json, from tests/test_suffixtree.rs:135-237).
+
+The restatement orders bytes as Python does (unsigned); the byte-range cases
+hold the host solver to it at the edges of the admitted range (0x25, 0x7F,
+0x80, 0xFF), and tests/test_gpu_compare.py runs the same cases on the kernels."""
 import json
 import os
 import random
@@ -94,6 +98,28 @@ def random_pairs(count=6, seed=5, hi=300, alphabet=b"ACGT"):
     return out
 
 
+# The admitted byte range at its edges: the lowest admitted byte next to the
+# highest, the two sides of the signed-char line, and all four together.
+BYTE_ALPHABETS = (b"\x25\xff", b"\x7f\x80", b"\x25\x7f\x80\xff")
+
+_byte_range = {}
+
+
+def byte_range_cases(alphabet):
+    """[(a, b, ref_lcs(a, b), ref_compare(a, b))] over `alphabet`: 100 seeded
+    pairs of 1..40 bytes and the periodic shapes with their letters mapped
+    onto the alphabet in rising and in falling order, each pair in both
+    argument orders.  Computed once per alphabet and shared (CPU and GPU tests)."""
+    if alphabet not in _byte_range:
+        pairs = tie_pairs(100, seed=17, alphabet=alphabet)
+        for letters in (alphabet, alphabet[::-1]):
+            to = bytes.maketrans(b"ABC", bytes(letters[k % len(letters)] for k in range(3)))
+            pairs += [(a.translate(to), b.translate(to)) for a, b in periodic_pairs()]
+        pairs += [(b, a) for a, b in pairs]
+        _byte_range[alphabet] = [(a, b, ref_lcs(a, b), ref_compare(a, b)) for a, b in pairs]
+    return _byte_range[alphabet]
+
+
 def test_restatement_matches_reference_fixtures():
     for name, a, b, want, small in vectors():
         if small and want is not None:
@@ -134,6 +160,27 @@ def test_host_solver_two_letter_ties(gx):
 def test_host_solver_random_pairs(gx):
     for a, b in random_pairs():
         assert gx.common_substring_host(a, b) == ref_lcs(a, b), (a, b)
+
+
+@pytest.mark.parametrize("alphabet", BYTE_ALPHABETS, ids=lambda s: s.hex())
+def test_host_solver_full_byte_range(gx, alphabet):
+    """The tie rule orders bytes (resolve, suffix_less: memcmp) and so does the
+    restatement (Python's bytes order): both unsigned, across 0x7F / 0x80 and
+    from the lowest admitted byte 0x25 to 0xFF."""
+    for a, b, want_lcs, want_cmp in byte_range_cases(alphabet):
+        assert gx.common_substring_host(a, b) == want_lcs, (a, b)
+        assert gx.compare_pair(a, b, host=True) == want_cmp, (a, b)
+
+
+def test_knob_clamps(gx, monkeypatch):
+    """GX_COMPARE_SEG_H is read on every call and clamped to [8, 32768]
+    (the tile element keeps its runs in 16 bits); a non-number is the default."""
+    for value, want in ((0, 8), (1, 8), (7, 8), (8, 8), (9, 9), (32768, 32768), (32769, 32768), (10**12, 32768),
+                        ("x", 1024)):
+        monkeypatch.setenv("GX_COMPARE_SEG_H", str(value))
+        assert gx.compare_segment_height() == want, value
+    monkeypatch.delenv("GX_COMPARE_SEG_H")
+    assert gx.compare_segment_height() == 1024
 
 
 def test_host_compare_pair(gx):
