@@ -9,6 +9,7 @@
 //   gx_api_staged.cpp   device-resident (staged) batches, the benchmark path
 //   gx_api_compare.cpp  compare mode: longest-common-substring recursion (main.rs:216-379)
 //   gx_api_suffix.cpp   suffix-tree mode: BWT and tree statistics from the suffix array (main.rs:154-215)
+//   gx_api_search.cpp   search mode: a kept suffix index and batched exact-match queries on it
 // Not a public header: host code only, one library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -329,6 +330,9 @@ struct gx_context {
     uint64_t suf_rounds = 0, suf_passes = 0;
     uint64_t suf_digit_passes[8] = {};
     double suf_sort_ms = 0.0, suf_lcp_ms = 0.0, suf_fold_ms = 0.0;
+    // the last search (gx_search_info; gx_api_search.cpp)
+    uint64_t srch_words = 0;
+    double srch_ms = 0.0, srch_locate_ms = 0.0;
 };
 
 struct PairHost {
@@ -547,6 +551,34 @@ int batch_core_steps(gx_context* ctx, const std::vector<PairHost>& ph,
                      std::vector<Walk>& walks, double* fill_ms, const uint8_t* chars_dev,
                      const std::vector<size_t>* off1, const std::vector<size_t>* off2,
                      const SmallAlpha* staged_alpha, const PassSet* alt = nullptr);
+
+// suffix arrays (gx_api_suffix.cpp), shared with the suffix index (gx_api_search.cpp)
+struct SufInfo {
+    uint64_t rounds = 0, passes = 0;
+    uint64_t digit_passes[8] = {};   // passes per digit byte (bits 8p .. 8p+7), over all rounds, round 0 included
+    double sort_ms = 0, lcp_ms = 0, fold_ms = 0;
+};
+// The device buffers of one suffix-array construction.  After suffix_device_sa
+// the text is in `text`, the suffix array in v[cur] and the ranks in `rank`.
+struct SufDev {
+    DevBuf text, k[2], v[2], rank, flags, table, tmp, small, fold, bwt;
+    int cur = 0;
+    uint64_t h = 8;            // the last doubling offset: max LCP < h
+    uint64_t* pin = nullptr;   // the context's pinned staging words
+    void release(gx_context* ctx) {
+        for (DevBuf* b : {&text, &k[0], &k[1], &v[0], &v[1], &rank, &flags, &table, &tmp, &small, &fold, &bwt})
+            pool_put(ctx, *b);
+    }
+};
+// t: N bytes ending in '$' and kSufPad zero bytes.  The caller holds ctx->mu.
+// Text to device text and device suffix array: the doubling loop.  Returns
+// with the stream idle; on an error every buffer of `w` is back in the pool.
+// with_stats / with_bwt: take the fold's and the BWT's buffers too.
+int suffix_device_sa(gx_context* ctx, const uint8_t* t, uint32_t N, bool with_stats, bool with_bwt, SufDev& w,
+                     SufInfo& info);
+// The host solver's suffix array of the same t; rank: its inverse.
+void suffix_host_sa(const uint8_t* t, size_t N, std::vector<uint32_t>& sa, std::vector<uint32_t>& rank);
+uint64_t suffix_host_below();   // GX_SUFFIX_HOST_BELOW
 
 // Labels the walk (algo.rs:339-422).  The interior moves come from `src`,
 // which calls emit(code) per move (0 sub, 1 insert, 2 delete) while emit

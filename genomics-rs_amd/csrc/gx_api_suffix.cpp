@@ -6,9 +6,12 @@
 //   host solver    suffix_host: prefix doubling with std::sort, Kasai's LCP and
 //                  a stack fold, no device: the checker on a CPU-only machine,
 //                  the baseline, and the path below GX_SUFFIX_HOST_BELOW
-//   device driver  suffix_device: the same doubling with radix sorts and scans
-//                  (gx_suffix.hip); one synchronisation per round, for the
-//                  convergence word and the next round's pass-skip masks
+//   device driver  suffix_device_sa: the same doubling with radix sorts and
+//                  scans (gx_suffix.hip), text to device text + device suffix
+//                  array; one synchronisation per round, for the convergence
+//                  word and the next round's pass-skip masks.  The suffix
+//                  index of search mode (gx_api_search.cpp) calls it too.
+//                  suffix_device: what follows it here: LCP, fold, BWT, copies
 //   Display        gx_format_suffix_stats (display.rs:8-38)
 #include <charconv>
 #include <cmath>
@@ -56,14 +59,18 @@ void kasai_host(const uint8_t* t, const uint32_t* sa, const uint32_t* rank, size
     }
 }
 
+}  // namespace
+
+uint64_t suffix_host_below() { return suf_env_u64("GX_SUFFIX_HOST_BELOW", kSuffixHostBelowDefault); }
+
 // t: N = n + 1 bytes ending in '$', followed by 8 zero bytes.
-void suffix_host(const uint8_t* t, size_t N, SufArrays& o) {
+void suffix_host_sa(const uint8_t* t, size_t N, std::vector<uint32_t>& sa, std::vector<uint32_t>& rank) {
     struct Item {
         uint64_t key;
         uint32_t idx;
     };
     std::vector<Item> it(N);
-    std::vector<uint32_t> rank(N);
+    rank.assign(N, 0);
     for (size_t i = 0; i < N; ++i) {
         uint64_t k = 0;
         for (int q = 0; q < 8; ++q) k = (k << 8) | t[i + q];
@@ -81,8 +88,15 @@ void suffix_host(const uint8_t* t, size_t N, SufArrays& o) {
         for (size_t i = 0; i < N; ++i)
             it[i] = Item{((uint64_t)rank[i] << 32) | (i + h < N ? rank[i + h] : 0u), (uint32_t)i};
     }
-    o.sa.resize(N);
-    for (size_t k = 0; k < N; ++k) o.sa[k] = it[k].idx;
+    sa.resize(N);
+    for (size_t k = 0; k < N; ++k) sa[k] = it[k].idx;
+}
+
+namespace {
+
+void suffix_host(const uint8_t* t, size_t N, SufArrays& o) {
+    std::vector<uint32_t> rank;
+    suffix_host_sa(t, N, o.sa, rank);
     kasai_host(t, o.sa.data(), rank.data(), N, o.lcp);
 }
 
@@ -124,28 +138,8 @@ void bwt_host(const uint8_t* t, const uint32_t* sa, size_t N, uint8_t* bwt) {
 // (GX_SUFFIX_LCP_BUDGET).  2^40 is about 130 times the A^(1 Mi) launch.
 constexpr uint64_t kSuffixLcpBudgetDefault = 1ull << 40;
 
-struct SufInfo {
-    uint64_t rounds = 0, passes = 0;
-    uint64_t digit_passes[8] = {};   // passes per digit byte (bits 8p .. 8p+7), over all rounds, round 0 included
-    double sort_ms = 0, lcp_ms = 0, fold_ms = 0;
-};
+}  // namespace
 
-// t: N bytes ending in '$' and kSufPad zero bytes.  The caller holds ctx->mu.
-int suffix_device(gx_context* ctx, const uint8_t* t, uint32_t N, gx_suffix_stats* out, uint8_t* bwt, uint32_t* sa,
-                  uint32_t* lcp, SufInfo& info) {
-    hipStream_t st = ctx->stream;
-    const size_t tiles = suf_tiles(N);
-    const size_t table_n = 256 * tiles;
-    const size_t tmp_n = std::max(suf_tiles(table_n), tiles);
-    const size_t nfb = (N + (size_t)kSufFoldBlock - 1) / kSufFoldBlock;
-    DevBuf d_text, d_k[2], d_v[2], d_rank, d_flags, d_table, d_tmp, d_small, d_fold, d_bwt;
-    auto done = [&](int rc) {
-        if (rc != GX_OK) (void)hipStreamSynchronize(st);   // nothing of this call still runs on the buffers
-        for (DevBuf* b : {&d_text, &d_k[0], &d_k[1], &d_v[0], &d_v[1], &d_rank, &d_flags, &d_table, &d_tmp, &d_small,
-                          &d_fold, &d_bwt})
-            pool_put(ctx, *b);
-        return rc;
-    };
 #define SUF_TRY(expr)                                                                                         \
     do {                                                                                                      \
         hipError_t e_ = (expr);                                                                               \
@@ -158,35 +152,51 @@ int suffix_device(gx_context* ctx, const uint8_t* t, uint32_t N, gx_suffix_stats
         const int rc_ = pool_get(ctx, (bytes), &(buf), st);                     \
         if (rc_ != GX_OK) return done(rc_);                                     \
     } while (0)
-    SUF_GET(d_text, (size_t)N + kSufPad);
+
+// Text to device text and device suffix array (gx_api.h): what suffix-tree
+// mode and the suffix index (gx_api_search.cpp) share.
+int suffix_device_sa(gx_context* ctx, const uint8_t* t, uint32_t N, bool with_stats, bool with_bwt, SufDev& w,
+                     SufInfo& info) {
+    hipStream_t st = ctx->stream;
+    const size_t tiles = suf_tiles(N);
+    const size_t table_n = 256 * tiles;
+    const size_t tmp_n = std::max(suf_tiles(table_n), tiles);
+    const size_t nfb = (N + (size_t)kSufFoldBlock - 1) / kSufFoldBlock;
+    auto done = [&](int rc) {
+        if (rc != GX_OK) {
+            (void)hipStreamSynchronize(st);   // nothing of this call still runs on the buffers
+            w.release(ctx);
+        }
+        return rc;
+    };
+    SUF_GET(w.text, (size_t)N + kSufPad);
     for (int q = 0; q < 2; ++q) {
-        SUF_GET(d_k[q], (size_t)N * 8);
-        SUF_GET(d_v[q], (size_t)N * 4);
+        SUF_GET(w.k[q], (size_t)N * 8);
+        SUF_GET(w.v[q], (size_t)N * 4);
     }
-    SUF_GET(d_rank, (size_t)N * 4);
-    SUF_GET(d_flags, (size_t)N * 4);
-    SUF_GET(d_table, table_n * 4);
-    SUF_GET(d_tmp, tmp_n * 4);
-    SUF_GET(d_small, 64);
-    SUF_GET(d_fold, nfb * 28);
-    if (bwt) SUF_GET(d_bwt, (size_t)N);
+    SUF_GET(w.rank, (size_t)N * 4);
+    SUF_GET(w.flags, (size_t)N * 4);
+    SUF_GET(w.table, table_n * 4);
+    SUF_GET(w.tmp, tmp_n * 4);
+    SUF_GET(w.small, 64);
+    if (with_stats) SUF_GET(w.fold, nfb * 28);
+    if (with_bwt) SUF_GET(w.bwt, (size_t)N);
     // device words: [0] OR of the keys, [1] their AND, [2] the last rank, [4..8) the fold
-    uint64_t* d_masks = (uint64_t*)d_small.p;
+    uint64_t* d_masks = (uint64_t*)w.small.p;
     uint32_t* d_last = (uint32_t*)(d_masks + 2);
-    SufFold* d_res = (SufFold*)(d_masks + 4);
     // pinned words: [0..2) the masks' presets, [2..5) masks and last rank as read back, [8..12) the fold
-    uint64_t* pin = (uint64_t*)io_pinned(ctx, 128);
+    uint64_t* pin = w.pin = (uint64_t*)io_pinned(ctx, 128);
     if (!pin) return done(fail(GX_ENOMEM, "suffix: pinned staging"));
     pin[0] = 0;
     pin[1] = ~0ull;
-    const uint8_t* text = (const uint8_t*)d_text.p;
-    uint32_t* rank = (uint32_t*)d_rank.p;
-    uint32_t* flags = (uint32_t*)d_flags.p;
+    const uint8_t* text = (const uint8_t*)w.text.p;
+    uint32_t* rank = (uint32_t*)w.rank.p;
+    uint32_t* flags = (uint32_t*)w.flags.p;
     int cur = 0;
-    auto K = [&](int q) { return (uint64_t*)d_k[q].p; };
-    auto V = [&](int q) { return (uint32_t*)d_v[q].p; };
+    auto K = [&](int q) { return (uint64_t*)w.k[q].p; };
+    auto V = [&](int q) { return (uint32_t*)w.v[q].p; };
     // (a pageable source: the copy has left `t` once the stream is synchronised below)
-    SUF_TRY(hipMemcpyAsync(d_text.p, t, (size_t)N + kSufPad, hipMemcpyHostToDevice, st));
+    SUF_TRY(hipMemcpyAsync(w.text.p, t, (size_t)N + kSufPad, hipMemcpyHostToDevice, st));
     SUF_TRY(hipMemcpyAsync(d_masks, pin, 16, hipMemcpyHostToDevice, st));
     SUF_TRY(launch_suf_keys0(text, N, K(cur), V(cur), d_masks, st));
     SUF_TRY(hipMemcpyAsync(pin + 2, d_masks, 16, hipMemcpyDeviceToHost, st));
@@ -198,14 +208,14 @@ int suffix_device(gx_context* ctx, const uint8_t* t, uint32_t N, gx_suffix_stats
         SUF_TRY(hipEventRecord(ctx->ev0, st));
         for (int p = 0; p < 8; ++p) {
             if (!((diff >> (8 * p)) & 0xffull)) continue;   // the same digit in every key
-            SUF_TRY(launch_suf_sort_pass(K(cur), V(cur), K(cur ^ 1), V(cur ^ 1), N, 8 * p, (uint32_t*)d_table.p,
-                                         (uint32_t*)d_tmp.p, st));
+            SUF_TRY(launch_suf_sort_pass(K(cur), V(cur), K(cur ^ 1), V(cur ^ 1), N, 8 * p, (uint32_t*)w.table.p,
+                                         (uint32_t*)w.tmp.p, st));
             cur ^= 1;
             ++info.passes;
             ++info.digit_passes[p];
         }
         SUF_TRY(hipEventRecord(ctx->ev1, st));
-        SUF_TRY(launch_suf_ranks(K(cur), V(cur), N, flags, (uint32_t*)d_tmp.p, rank, d_last, st));
+        SUF_TRY(launch_suf_ranks(K(cur), V(cur), N, flags, (uint32_t*)w.tmp.p, rank, d_last, st));
         // the next round's keys and masks ride along (unused when this round was the last)
         SUF_TRY(hipMemcpyAsync(d_masks, pin, 16, hipMemcpyHostToDevice, st));
         SUF_TRY(launch_suf_keys(rank, N, (uint32_t)h, K(cur ^ 1), V(cur ^ 1), d_masks, st));
@@ -217,7 +227,37 @@ int suffix_device(gx_context* ctx, const uint8_t* t, uint32_t N, gx_suffix_stats
         if ((uint32_t)pin[4] == N - 1) break;
         cur ^= 1;
     }
-    const uint32_t* d_sa = V(cur);
+    w.cur = cur;
+    w.h = h;
+    return GX_OK;
+}
+
+namespace {
+
+// t: N bytes ending in '$' and kSufPad zero bytes.  The caller holds ctx->mu.
+int suffix_device(gx_context* ctx, const uint8_t* t, uint32_t N, gx_suffix_stats* out, uint8_t* bwt, uint32_t* sa,
+                  uint32_t* lcp, SufInfo& info) {
+    hipStream_t st = ctx->stream;
+    const size_t nfb = (N + (size_t)kSufFoldBlock - 1) / kSufFoldBlock;
+    SufDev w;
+    {
+        const int rc = suffix_device_sa(ctx, t, N, true, bwt != nullptr, w, info);
+        if (rc != GX_OK) return rc;
+    }
+    auto done = [&](int rc) {
+        if (rc != GX_OK) (void)hipStreamSynchronize(st);   // nothing of this call still runs on the buffers
+        w.release(ctx);
+        return rc;
+    };
+    DevBuf &d_fold = w.fold, &d_bwt = w.bwt;
+    uint64_t* d_masks = (uint64_t*)w.small.p;
+    SufFold* d_res = (SufFold*)(d_masks + 4);
+    uint64_t* pin = w.pin;
+    const uint8_t* text = (const uint8_t*)w.text.p;
+    uint32_t* rank = (uint32_t*)w.rank.p;
+    uint32_t* flags = (uint32_t*)w.flags.p;
+    const uint64_t h = w.h;
+    const uint32_t* d_sa = (const uint32_t*)w.v[w.cur].p;
     // all ranks differ, so max LCP < h: the bound on the LCP kernel's and the fold's work
     const uint64_t lanes = ((uint64_t)N + kSufLcpChunk - 1) / kSufLcpChunk;
     if (lanes * (h / 8) > suf_env_u64("GX_SUFFIX_LCP_BUDGET", kSuffixLcpBudgetDefault)) {
@@ -256,8 +296,6 @@ int suffix_device(gx_context* ctx, const uint8_t* t, uint32_t N, gx_suffix_stats
     SufFold f;
     memcpy(&f, pin + 8, sizeof f);
     done(GX_OK);   // (the stream is idle)
-#undef SUF_TRY
-#undef SUF_GET
     out->num_internal = f.num_internal;
     out->num_leaves = N;
     out->num_nodes = f.num_internal + N + 1;
@@ -266,6 +304,9 @@ int suffix_device(gx_context* ctx, const uint8_t* t, uint32_t N, gx_suffix_stats
     out->longest_repeat_start = f.repeat_start;
     return GX_OK;
 }
+
+#undef SUF_TRY
+#undef SUF_GET
 
 // Rust's `{}` of an f64: the shortest digits that round-trip, never an exponent.
 std::string suf_f64(double v) {

@@ -37,6 +37,14 @@
 //       the "Stats:" block is printed.  An alphabet file, when given, is
 //       checked as the reference's tree checks it; --suffix-links is accepted
 //       and ignored; the Graphviz block of small trees is not printed.
+//
+//   gx-align search -f genome.fasta -p patterns.fasta [--max-hits K] [-o hits.tsv]
+//       No counterpart in the reference's main.rs: where every record of
+//       patterns.fasta occurs in the first record of genome.fasta, from a
+//       suffix index kept on the GPU (gx_suffix_index_search).
+//       One TSV line per pattern, to stdout unless -o: name, length, count,
+//       prefix_len, prefix_pos and up to K (default 16) 0-based ascending
+//       positions, comma-separated.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -61,7 +69,8 @@ void usage() {
             "[-o <TSV>] [-g|--gpus <N>] [--no-self]\n"
             "       gx-align compare -d|--fasta-dir <DIR> [-o <TSV>]\n"
             "       gx-align suffix-tree -f|--fasta-path <FASTA> [-a|--alphabet-file <ALPHABET>] [--suffix-links] "
-            "[--stats] [-o <BWT>]\n");
+            "[--stats] [-o <BWT>]\n"
+            "       gx-align search -f|--fasta-path <GENOME> -p|--patterns <PATTERNS> [--max-hits <K>] [-o <TSV>]\n");
 }
 
 struct Records {
@@ -438,13 +447,72 @@ int run_suffix_tree(const std::string& fasta, const std::string& alphabet, bool 
     return 0;
 }
 
+// Search mode on GPU 0 (no counterpart in the reference): every record of the
+// pattern file against the suffix index of the genome's first record.
+int run_search(const std::string& fasta, const std::string& patterns, uint32_t max_hits, const std::string& out_path) {
+    const char* lg = getenv("GX_LOG");
+    const bool info = lg && (!strcmp(lg, "info") || !strcmp(lg, "debug"));
+    if (info) fprintf(stderr, "[INFO] MODE: Search\n[INFO] Loading sequences from %s and %s\n", fasta.c_str(), patterns.c_str());
+    Records g, q;
+    load_fasta(fasta, g);
+    load_fasta(patterns, q);
+    if (!g.size()) { fprintf(stderr, "[ERROR] no record in %s\n", fasta.c_str()); return 1; }
+    const size_t npat = q.size();
+    std::vector<uint8_t> packed;
+    std::vector<uint64_t> off(npat + 1, 0);
+    for (size_t p = 0; p < npat; ++p) {
+        packed.insert(packed.end(), q.seq(p), q.seq(p) + q.sl[p]);
+        off[p + 1] = packed.size();
+    }
+    gx_context* ctx = nullptr;
+    if (gx_context_create(0, &ctx) != GX_OK) return fail_msg("context", 1);
+    gx_suffix_index* idx = nullptr;
+    auto t0 = std::chrono::steady_clock::now();
+    int rc = gx_suffix_index_build(ctx, g.seq(0), g.sl[0], &idx);
+    if (rc != GX_OK) { gx_context_destroy(ctx); return fail_msg("search: index", rc); }
+    const auto build_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+    std::vector<gx_search_hit> hits(npat);
+    std::vector<uint64_t> hoff(npat + 1, 0);
+    std::vector<uint32_t> pos(std::max<size_t>(1, npat * (size_t)std::min<uint64_t>(max_hits, 16)));
+    t0 = std::chrono::steady_clock::now();
+    for (int pass = 0; pass < 2; ++pass) {   // GX_ECAP: hit_offsets is complete; allocate and repeat
+        rc = gx_suffix_index_search(idx, packed.data(), off.data(), npat, hits.data(), max_hits,
+                                    max_hits ? pos.data() : nullptr, pos.size(), max_hits ? hoff.data() : nullptr);
+        if (rc != GX_ECAP) break;
+        pos.assign((size_t)hoff[npat], 0);
+    }
+    const auto us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+    if (rc == GX_OK && info) {
+        uint64_t words = 0;
+        double sms = 0, lms = 0;
+        gx_search_info(ctx, &words, &sms, &lms);
+        fprintf(stderr, "[INFO] index of %llu bases built in %lld us; %zu patterns searched in %lld us "
+                        "(%llu word compares, interval kernel %.3f ms, locate %.3f ms)\n",
+                (unsigned long long)g.sl[0], (long long)build_us, npat, (long long)us, (unsigned long long)words, sms, lms);
+    }
+    gx_suffix_index_free(idx);
+    gx_context_destroy(ctx);
+    if (rc != GX_OK) return fail_msg("search", rc);
+    FILE* f = out_path.empty() ? stdout : fopen(out_path.c_str(), "w");
+    if (!f) { fprintf(stderr, "[ERROR] cannot write %s\n", out_path.c_str()); return 1; }
+    for (size_t p = 0; p < npat; ++p) {
+        fprintf(f, "%s\t%llu\t%u\t%u\t%u\t", q.name(p).c_str(), (unsigned long long)q.sl[p], hits[p].count,
+                hits[p].prefix_len, hits[p].prefix_pos);
+        for (uint64_t k = hoff[p]; k < hoff[p + 1]; ++k) fprintf(f, k == hoff[p] ? "%u" : ",%u", pos[k]);
+        fputc('\n', f);
+    }
+    if (f != stdout) fclose(f);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
     // main.rs:91-96: the CLI logs at info unless told otherwise
     setenv("GX_LOG", getenv("GX_LOG") ? getenv("GX_LOG") : "info", 1);
-    std::string config = "config.toml", type, fasta, dir, tsv = "similarity_matrix.tsv", mode;
+    std::string config = "config.toml", type, fasta, dir, tsv = "similarity_matrix.tsv", mode, patterns;
     int ngpu = 0;
+    long long max_hits = 16;
     bool with_self = true, stats = false, out_set = false;
     for (int k = 1; k < argc; ++k) {
         std::string a = argv[k];
@@ -453,24 +521,28 @@ int main(int argc, char** argv) {
             dst = argv[++k];
         };
         if (a == "-c" || a == "--config-path") next(config);
-        else if (a == "align" || a == "all-vs-all" || a == "compare" || a == "suffix-tree") mode = a;
+        else if (a == "align" || a == "all-vs-all" || a == "compare" || a == "suffix-tree" || a == "search") mode = a;
         else if (a == "-a" || a == "--alignment-type" || a == "--alphabet-file") next(type);   // (suffix-tree: the alphabet)
         else if (a == "-f" || a == "--fasta-path") next(fasta);
         else if (a == "-d" || a == "--fasta-dir") next(dir);
         else if (a == "-o" || a == "--output") { next(tsv); out_set = true; }
         else if (a == "--stats") stats = true;
+        else if (a == "-p" || a == "--patterns") next(patterns);
+        else if (a == "--max-hits") { std::string v; next(v); max_hits = atoll(v.c_str()); }
         else if (a == "--suffix-links") {}   // (the reference's build strategy: no counterpart)
         else if (a == "-g" || a == "--gpus") { std::string v; next(v); ngpu = atoi(v.c_str()); }
         else if (a == "--no-self") with_self = false;
         else if (a == "-h" || a == "--help") { usage(); return 0; }
         else { usage(); return 2; }
     }
-    const bool by_file = mode == "align" || mode == "suffix-tree";
-    if (mode.empty() || (by_file && fasta.empty()) || (!by_file && dir.empty())) {
+    const bool by_file = mode == "align" || mode == "suffix-tree" || mode == "search";
+    if (mode.empty() || (by_file && fasta.empty()) || (!by_file && dir.empty()) ||
+        (mode == "search" && (patterns.empty() || max_hits < 0 || max_hits > 0xFFFFFFFFll))) {
         usage();
         return 2;
     }
     if (mode == "compare") return run_compare(dir, tsv);   // (reads no scores: main.rs:216-221)
+    if (mode == "search") return run_search(fasta, patterns, (uint32_t)max_hits, out_set ? tsv : std::string());
     if (mode == "suffix-tree") return run_suffix_tree(fasta, type, stats, out_set ? tsv : std::string());
     gx_scores sc;
     if (gx_config_load(config.c_str(), &sc) != GX_OK) {

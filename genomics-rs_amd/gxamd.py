@@ -94,7 +94,9 @@ EXPORTED = ["gx_last_error", "gx_version", "gx_context_create", "gx_context_dest
             "gx_common_substring_host", "gx_common_substring", "gx_compare_pair", "gx_compare_matrix",
             "gx_compare_info", "gx_compare_batches", "gx_compare_segment_height", "gx_compare_run_stats",
             "gx_common_substring_candidates_host",
-            "gx_suffix_tree_stats", "gx_suffix_info", "gx_suffix_digit_passes", "gx_suffix_tile", "gx_format_suffix_stats"]
+            "gx_suffix_tree_stats", "gx_suffix_info", "gx_suffix_digit_passes", "gx_suffix_tile", "gx_format_suffix_stats",
+            "gx_suffix_index_build", "gx_suffix_index_free", "gx_suffix_index_info", "gx_suffix_index_export",
+            "gx_suffix_index_search", "gx_search_info"]
 
 _lib = None
 
@@ -172,6 +174,13 @@ def lib():
     L.gx_suffix_digit_passes.argtypes = [vp, u64p]
     L.gx_suffix_tile.argtypes = [ip, ip, ip]
     L.gx_format_suffix_stats.argtypes = [ctypes.POINTER(CSuffixStats), vp, sz, vp, sz, ctypes.POINTER(sz)]
+    L.gx_suffix_index_build.argtypes = [vp, vp, sz, ctypes.POINTER(vp)]
+    L.gx_suffix_index_free.argtypes = [vp]
+    L.gx_suffix_index_free.restype = None
+    L.gx_suffix_index_info.argtypes = [vp, u64p, ip, u64p]
+    L.gx_suffix_index_export.argtypes = [vp, vp]
+    L.gx_suffix_index_search.argtypes = [vp, vp, vp, sz, vp, ctypes.c_uint32, vp, sz, vp]
+    L.gx_search_info.argtypes = [vp, u64p, dp, dp]
     _lib = L
     return L
 
@@ -981,6 +990,102 @@ def suffix_tile() -> Tuple[int, int, int]:
     return v[0].value, v[1].value, v[2].value
 
 
+# ---------------------------------------------------------------------------
+# search mode (no counterpart in the reference)
+
+HIT_DTYPE = np.dtype([("lo", "<u4"), ("count", "<u4"), ("prefix_len", "<u4"), ("prefix_pos", "<u4")])
+ALL_HITS = 0xFFFFFFFF   # max_hits: every occurrence
+_FIRST_CAP = 1 << 22    # positions asked for before the count is known (GX_ECAP names the rest)
+
+
+class SuffixIndex:
+    """The suffix index of seq (gx_suffix_index): with a context, text and suffix array stay on the
+    device until close() and every search runs there; host=True keeps both on the host (no device).
+    Close it before its context."""
+
+    def __init__(self, seq: bytes, ctx: Optional["Context"] = None, host: bool = False):
+        self.ptr = None
+        self._ctx = None if host else (ctx or default_context())
+        ks, ps = _buf(seq)
+        p = ctypes.c_void_p()
+        _check(lib().gx_suffix_index_build(self._ctx.ptr if self._ctx else None, ps, len(seq), ctypes.byref(p)))
+        self.ptr = p
+        self.n = len(seq)
+
+    def search(self, patterns, max_hits: int = 0) -> dict:
+        """gx_suffix_index_search for a batch: `patterns` is a sequence of bytes, or (packed, offsets) with
+        pattern p = packed[offsets[p]:offsets[p + 1]].  Returns uint32 arrays "lo", "count", "prefix_len",
+        "prefix_pos" (one entry per pattern) and, with max_hits > 0, "positions" (the first
+        min(count, max_hits) suffix-array entries of each pattern's interval, ascending) and "hit_offsets"
+        (uint64, npat + 1).  max_hits = ALL_HITS reports every occurrence."""
+        if isinstance(patterns, tuple):
+            packed, off = patterns
+            packed = np.ascontiguousarray(np.frombuffer(packed, np.uint8) if isinstance(packed, (bytes, bytearray))
+                                          else packed, np.uint8)
+            off = np.ascontiguousarray(off, np.uint64)
+        else:
+            packed = np.frombuffer(b"".join(patterns), np.uint8)
+            off = np.zeros(len(patterns) + 1, np.uint64)
+            np.cumsum(np.fromiter((len(x) for x in patterns), np.uint64, len(patterns)), out=off[1:])
+        npat = len(off) - 1
+        if packed.size == 0:
+            packed = np.zeros(1, np.uint8)
+        hits = np.zeros(npat, HIT_DTYPE)
+        out = None
+        if max_hits <= 0:
+            _check(lib().gx_suffix_index_search(self.ptr, packed.ctypes.data, off.ctypes.data, npat, hits.ctypes.data,
+                                                0, None, 0, None))
+        else:
+            hoff = np.zeros(npat + 1, np.uint64)
+            cap = max(1, min(npat * min(max_hits, self.n + 1), _FIRST_CAP))
+            for _ in range(2):
+                pos = np.zeros(cap, np.uint32)
+                rc = lib().gx_suffix_index_search(self.ptr, packed.ctypes.data, off.ctypes.data, npat, hits.ctypes.data,
+                                                  max_hits, pos.ctypes.data, cap, hoff.ctypes.data)
+                if rc != 7:
+                    break
+                cap = int(hoff[-1])   # GX_ECAP: hit_offsets is complete; allocate and repeat
+            _check(rc)
+            out = {"positions": pos[:int(hoff[-1])], "hit_offsets": hoff}
+        r = {k: np.ascontiguousarray(hits[k]) for k in ("lo", "count", "prefix_len", "prefix_pos")}
+        if out:
+            r.update(out)
+        return r
+
+    def sa(self) -> np.ndarray:
+        """The suffix array, n + 1 entries (gx_suffix_index_export)."""
+        a = np.zeros(self.n + 1, np.uint32)
+        _check(lib().gx_suffix_index_export(self.ptr, a.ctypes.data))
+        return a
+
+    def info(self) -> dict:
+        n, dev, b = ctypes.c_uint64(), ctypes.c_int(), ctypes.c_uint64()
+        _check(lib().gx_suffix_index_info(self.ptr, ctypes.byref(n), ctypes.byref(dev), ctypes.byref(b)))
+        return {"n": n.value, "on_device": bool(dev.value), "device_bytes": b.value}
+
+    def close(self):
+        if self.ptr:
+            lib().gx_suffix_index_free(self.ptr)
+            self.ptr = None
+
+    def __del__(self):
+        try:
+            if self._ctx is None or self._ctx.ptr:   # (a device index does not outlive its context)
+                self.close()
+        except Exception:
+            pass
+
+
+def search_info(ctx: Optional["Context"] = None) -> dict:
+    """gx_search_info of the last search on ctx: 8-byte compare steps, device ms of the interval kernel
+    and of the locate step (clamp, scan, gather)."""
+    ctx = ctx or default_context()
+    w = ctypes.c_uint64()
+    ms = [ctypes.c_double() for _ in range(2)]
+    _check(lib().gx_search_info(ctx.ptr, ctypes.byref(w), *[ctypes.byref(x) for x in ms]))
+    return {"word_compares": w.value, "search_ms": ms[0].value, "locate_ms": ms[1].value}
+
+
 # STRING_TERMINATORS (tree.rs:66-69)
 _TERMINATORS = "$!@#%^&*()-_=+{}[]|;:'<>,.?/~` \n"
 
@@ -1025,6 +1130,15 @@ class SuffixTree:
         """get_lcs (tree.rs:218-281): (i, j, length)."""
         a, b = self._bare(string_one_idx), self._bare(string_two_idx)
         return common_substring_host(a, b) if self._host else common_substring(a, b, self._ctx)
+
+    def find(self, pattern: str, string_idx: int = 0) -> List[int]:
+        """Every position of `pattern` in string `string_idx`, ascending (search mode, DESIGN.md 18;
+        the reference's tree has no such query).  The empty pattern matches at 0 .. len."""
+        idx = SuffixIndex(self._bare(string_idx), ctx=self._ctx, host=self._host)
+        try:
+            return idx.search([pattern.encode("latin-1")], max_hits=ALL_HITS)["positions"].tolist()
+        finally:
+            idx.close()
 
     def __str__(self):  # display.rs:40-56 without the Graphviz block
         return f"\nStats: {self.stats}\n"

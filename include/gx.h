@@ -433,6 +433,55 @@ int gx_suffix_tile(int* sort_items_per_wg, int* lcp_chunk, int* fold_block);
 int gx_format_suffix_stats(const gx_suffix_stats* st, const uint8_t* bwt, size_t bwt_len,
                            char* out, size_t cap, size_t* needed);
 
+/* ---- search mode (no counterpart in the reference's main.rs) ----------------
+ * "Where does this string occur?", for a batch of patterns, on the suffix
+ * array of t = s + '$' kept on the device.  Conventions as
+ * suffix-tree mode: N = n + 1, suffixes in plain unsigned byte order, text and
+ * pattern bytes above '$' (0x24).  A pattern P of m bytes, 0 <= m <= 65,535:
+ *   lo          the number of suffixes smaller than P (one that has P as a
+ *               prefix is not smaller)
+ *   count       the number of suffixes that have P as a prefix: SA[lo .. lo +
+ *               count), overlapping occurrences included
+ *   prefix_len  the longest prefix of P that occurs in t (m when count > 0)
+ *   prefix_pos  one position of it: SA[lo] when count > 0; otherwise, with
+ *               a = lcp(P, SA[lo - 1]) and b = lcp(P, SA[lo]) (0 when lo = N),
+ *               SA[lo - 1] if a >= b, else SA[lo]; 0 when prefix_len = 0
+ * m = 0: lo = 0, count = N, prefix_len = 0, prefix_pos = SA[0] = n. */
+typedef struct gx_suffix_index gx_suffix_index;   /* text + suffix array, device-resident (host with ctx = NULL) */
+typedef struct gx_search_hit { uint32_t lo, count, prefix_len, prefix_pos; } gx_search_hit;
+
+/* The index of s.  With a context it lives in device memory (N + 16 text bytes
+ * and 4 N suffix-array bytes from the context's pool, held until
+ * gx_suffix_index_free) and every search on it runs on the device; the array
+ * of an input shorter than GX_SUFFIX_HOST_BELOW comes from the host solver and
+ * is uploaded.  No LCP array is built (GX_SUFFIX_LCP_BUDGET does not apply).
+ * ctx = NULL: index and searches on the host, no device.  Errors as
+ * gx_suffix_tree_stats.  Indexes are freed before their context is destroyed;
+ * several may live on one context. */
+int  gx_suffix_index_build(gx_context* ctx, const uint8_t* s, size_t n, gx_suffix_index** out);
+void gx_suffix_index_free(gx_suffix_index* idx);
+/* n, whether the index is device-resident, and the device bytes it holds. */
+int  gx_suffix_index_info(const gx_suffix_index* idx, uint64_t* n, int* on_device, uint64_t* device_bytes);
+/* The suffix array, n + 1 entries. */
+int  gx_suffix_index_export(const gx_suffix_index* idx, uint32_t* sa /* n+1 */);
+/* Pattern p is patterns[offsets[p] .. offsets[p + 1]).  hits[p] as above.  With
+ * positions, pattern p reports q_p = min(count_p, max_hits) of its occurrences,
+ * SA[lo_p .. lo_p + q_p) sorted ascending, at positions[hit_offsets[p] ..
+ * hit_offsets[p + 1]).  GX_EINVAL: a pattern byte at or below '$' (the message
+ * names pattern and offset), offsets not non-decreasing from 0.  GX_ERANGE: a
+ * pattern longer than 65,535 bytes; total pattern bytes plus npat, or total
+ * reported positions, at or above 2^32.  GX_ECAP: positions_cap is below the
+ * total (named in gx_last_error()): hits[] and hit_offsets[] are complete,
+ * positions[] is untouched. */
+int  gx_suffix_index_search(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets /* npat+1 */,
+                            size_t npat, gx_search_hit* hits /* npat */, uint32_t max_hits,
+                            uint32_t* positions /* may be NULL: counts only */, size_t positions_cap,
+                            uint64_t* hit_offsets /* npat+1, may be NULL iff positions is NULL */);
+/* The last search on ctx: 8-byte compare steps of the interval kernel, its
+ * device time (ms) and that of the locate step (clamp, scan and gather; 0 for
+ * counts only).  Measurement and tests. */
+int  gx_search_info(const gx_context* ctx, uint64_t* word_compares, double* search_ms, double* locate_ms);
+
 #ifdef __cplusplus
 }
 #endif
