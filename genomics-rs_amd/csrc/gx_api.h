@@ -48,11 +48,11 @@ hipError_t launch_traceback(const TbDev* d_jobs, int njobs, int max_strips, bool
 hipError_t launch_export(const int32_t* plane, int32_t* out, int n, int m, int t4, int lay, int gshift, int row0,
                          int rows, hipStream_t st);
 hipError_t launch_export_w16(const uint8_t* codes, int half, int which, int32_t* out, int n, int m, int t4, int h,
-                             int g, int floor_, int gshift, int row0, int rows, hipStream_t st);
+                             int g, int floor_, int gshift, int row0, int rows, int rows_per_lane, hipStream_t st);
 hipError_t launch_export_d8(const uint8_t* pI, const uint8_t* px, int32_t* out, int n, int m, int t4, int h, int g,
                             int floor_, int gshift, int row0, int rows, hipStream_t st);
 hipError_t launch_plane_sums(const PairDev* d_pairs, int npairs, int max_strips, int lay, int mode, int h, int g,
-                             int floor_, int gshift, unsigned long long* out, hipStream_t st);
+                             int floor_, int gshift, unsigned long long* out, int rows_per_lane, hipStream_t st);
 hipError_t launch_local_col(const PairDev* d_pairs, int npairs, PairRes* d_pres, int h, int g, hipStream_t st);
 hipError_t launch_fill_cs2(int W, bool local, bool planes, bool tbl, const PairDev* d_pairs, int npairs,
                            int total_bands, int* d_counter, StripRes* d_sres, PairRes* d_pres, Scores32 sc, int grid,
@@ -65,7 +65,7 @@ int skew_lcs_sweep(int W);
 hipError_t launch_skew_max_col(const PairDev* d_pairs, int npairs, int mmax, PairRes* d_pres, int gshift, hipStream_t st);
 bool skew_traced(bool planes, bool trace, bool track);
 hipError_t launch_skew_codes(const PairDev* d_pairs, int npairs, int mmax, Scores32 sc, bool tbl, hipStream_t st);
-hipError_t launch_fill_pk(int W, int planes, const PairDev* d_pairs, int npairs, int ntwins, int total_bands,
+hipError_t launch_fill_pk(int W, int planes, int rows, const PairDev* d_pairs, int npairs, int ntwins, int total_bands,
                           int* d_counter, PairRes* d_pres, StripRes* d_sres, Scores32 sc, int grid, hipStream_t st);
 hipError_t launch_fill_wide(const WideDev* d_pairs, int npairs, WideScores sc, WideRes* d_res, int local, int track,
                             hipStream_t st);
@@ -302,6 +302,7 @@ struct gx_context {
     int last_pbits = 0;                              // ... its plane bits per cell (gx_fill_plane_bits)
     int last_chunks = 1;                             // chunks of the last staged / batch call
     int last_twin = 0;                               // the last fill was the twin (packed 16-bit) fill
+    int last_rows = 0;                               // ... its rows per lane (2 or 4; 0: not the twin fill)
     int last_groups = 1;                             // fill launches per pass of the last staged / batch call
     // GX_STAGED_PLANE_SUMS: plane checksums of every pass of a staged run
     DevBuf sums_dev;
@@ -361,6 +362,7 @@ struct FillJob {
     bool d8 = false;                    // compact byte planes (d8_planes_ok)
     bool shift = false;                 // values kept as V - (i + j) g (Scores32.shift)
     bool twin = false;                  // the twin fill (gx_fill_pk.hip): twin_table's pairs share every band
+    int rows = kRowsPerLane;            // twin fill: rows per lane (4: 256-row strips, gx_fill_pk.hip R)
     bool w16 = false;                   // twin plane codes, 2 B per cell (w16_ok; batches only)
     bool nocodes = false;               // w16 without code words: the traceback derives them from the planes
     bool noskel = false;                // nocodes without landing columns: the traceback walks the strips in sequence
@@ -376,6 +378,9 @@ struct FillJob {
     std::vector<WideDev> wd;
     std::vector<WideRes> wres;
 };
+
+// Rows per strip of a fill: its layout's, or 64 x rows per lane of a twin fill.
+inline int job_strip_rows(const FillJob& j) { return j.twin && j.lay == 0 ? kWave * j.rows : strip_rows(j.lay); }
 
 // A staged run's last fill, kept for gx_staged_table (its buffers go back to
 // the pool when the run is replaced and the last table of it is freed; the
@@ -493,12 +498,14 @@ int skew_band_waves();
 int cs2_band_waves(int total_strips, int grid_cap);
 bool skew_ok(const Scores32& sc, bool lcs_plane, size_t mmax);
 int fill_layout(const std::vector<PairHost>& ph, const Scores32& sc, int grid_cap, bool track, bool lcs_plane);
-long long twin_bound(const Scores32& sc, int W, long long dm, bool local = false);
-long long twin_gap_cap(const Scores32& sc, int W, bool local = false);
+long long twin_bound(const Scores32& sc, int W, long long dm, bool local = false, int rows = kRowsPerLane);
+long long twin_gap_cap(const Scores32& sc, int W, bool local = false, int rows = kRowsPerLane);
+bool twin_rows4_auto(int min_strips4, int twin_strips4, int grid_cap);
+int twin_rows4_band_waves(int twin_strips4, int grid_cap, int min_strips4);
 std::vector<std::pair<int, int>> twin_table(const std::vector<PairHost>& ph, long long gap_cap = 1024);
 int twin_width(const std::vector<PairHost>& ph, const std::vector<std::pair<int, int>>& tw, const Scores32& sc,
                int is_local, bool track, bool lcs, int lay, bool planes, bool d8, int W_want,
-               bool long_ok = false);
+               bool long_ok = false, int rows = kRowsPerLane);
 double pair_device_bytes(size_t n, size_t m, double plane_bpc);   // one pair's device bytes in a batch
 double chunk_budget(gx_context* ctx);                             // device bytes one chunk may use
 std::vector<std::pair<size_t, size_t>> plan_chunks(gx_context* ctx, const std::vector<PairHost>& ph,

@@ -241,13 +241,13 @@ static int batch_core_overlap(gx_context* ctx, const std::vector<PairHost>& ph,
         if (!prc)
             prc = run_fill(ctx, dproc[0][1], dph[0][1], sc, is_local, planes, false, false, pb, chars_dev,
                            chars_dev ? &o1[0][1] : nullptr, chars_dev ? &o2[0][1] : nullptr, &alpha, 2, false);
-        if (prc || !(pa.noskel && pb.noskel && pa.twin && pb.twin && pa.lay == pb.lay)) return kOverlapNo;
+        if (prc || !(pa.noskel && pb.noskel && pa.twin && pb.twin && pa.lay == pb.lay && pa.rows == pb.rows)) return kOverlapNo;
     }
     unsigned long long* const sums0 = ctx->sums_dst;
     HIPCHK(hipEventRecord(ctx->ev0, sA));
     int rc = fill(0, 0);
     if (!rc) { rc = fill(1, 0); jb_live = !rc; }
-    if (!rc && !(jA[0].noskel && jB.noskel && jA[0].lay == jB.lay && jA[0].twin && jB.twin)) {
+    if (!rc && !(jA[0].noskel && jB.noskel && jA[0].lay == jB.lay && jA[0].twin && jB.twin && jA[0].rows == jB.rows)) {
         drain();
         ctx->sums_dst = sums0;   // (the plain pipeline writes this pass's checksums again)
         return kOverlapNo;

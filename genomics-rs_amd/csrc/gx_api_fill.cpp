@@ -148,12 +148,48 @@ int run_fill(gx_context* ctx, const std::vector<std::pair<const uint8_t*, const 
     // planes (tables, GX_PLANES_W16=0) keep both.
     job.nocodes = w16;
     job.noskel = job.nocodes;
+    // Rows per lane.  Four (256-row strips, gx_fill_pk.hip R = 4) halve how
+    // often the band pipeline's per-step work runs per cell: the ring reads
+    // and pushes, the DPP hand-down, the counters and polls, the I/O wave's
+    // chunks and the band hand-off rows.  Only the global fill with twin
+    // codes and neither code words nor skeleton has that instantiation, and
+    // only launches whose admission bound holds at the taller strips
+    // (twin_bound's span, 320 instead of 192 neighbour steps a strip) take
+    // it; the band width is picked again on the 256-row strips.
+    // GX_TWIN_ROWS=2|4 forces the choice where it is launchable.  Unasked,
+    // four rows are taken only by the default launch: the rule was measured
+    // at the device's own grid and its own band width, so a launch whose band
+    // width or grid is given (GX_BAND_WAVES, GX_FILL_GRID) keeps two rows and
+    // the width it asked for (15-strip bands are not admitted at four rows).
+    int rows = kRowsPerLane;
+    if (twin && w16 && !is_local && !track && lay == 0) {
+        const int SR4 = kWave * kTwinRowsMax;
+        int strips4 = 0, min4 = INT_MAX;
+        for (const PairHost& h : ph) {
+            strips4 += ceil_div((int)h.n, SR4);
+            min4 = std::min(min4, ceil_div((int)h.n, SR4));
+        }
+        const char* e = getenv("GX_TWIN_ROWS");
+        const int force = e ? atoi(e) : 0;
+        const bool plain = !getenv("GX_BAND_WAVES") && !getenv("GX_FILL_GRID");
+        const bool want4 = force == 4 ||
+                           (force != 2 && plain && twin_rows4_auto(min4, strips4 / 2, fill_grid_cap(ctx->device)));
+        if (want4) {
+            const char* bw = getenv("GX_BAND_WAVES");
+            const int want = bw ? atoi(bw) : twin_rows4_band_waves(strips4 / 2, fill_grid_cap(ctx->device), min4);
+            const int W4 = twin_width(ph, tw, sc, is_local, track, lcs, lay, planes, d8, want, true, kTwinRowsMax);
+            if (W4 > 0) { rows = kTwinRowsMax; Wt = W4; }   // (not admitted at any width: two rows a lane)
+        }
+    }
+    job.rows = rows;
+    const int SRf = twin ? kWave * rows : SR;   // rows per strip of the launch
     // small-alphabet twins: the match test through score tables (cell_pk; the
     // shifted scores must fit an unsigned byte);
     // the byte-plane twin (tables) keeps the plain test
     const bool twin_tbl = twin && tbl && (!planes || w16) && scl.sm >= 0 && scl.sm <= 255 && scl.smm >= 0 &&
                           scl.smm <= 255;
     ctx->last_twin = twin ? 1 : 0;
+    ctx->last_rows = twin ? rows : 0;
     const int Wf = twin ? Wt : W;   // band width of the launch
     const size_t plane_esz = d8 ? 1 : sizeof(int32_t);
     job.W = Wf;
@@ -185,8 +221,9 @@ int run_fill(gx_context* ctx, const std::vector<std::pair<const uint8_t*, const 
             const PairHost& y = ph[mate[p]];
             ns = (int)std::max(ph[p].n, y.n); ms = (int)std::max(ph[p].m, y.m);
         }
-        d.strips = ceil_div(ns, SR);
+        d.strips = ceil_div(ns, SRf);
         d.bands = ceil_div(d.strips, Wf);
+        d.rows = twin ? rows : 0;
         // steps per strip: layout 0, lane 63 pushes column m at step m + 63; layout 1, column m at step m - 1
         const int T = lay == 1 ? ms + 1 : ms + kWave;
         d.t16 = ceil_div(T, 16);
@@ -199,7 +236,7 @@ int run_fill(gx_context* ctx, const std::vector<std::pair<const uint8_t*, const 
         c1o[p] = chars_bytes; chars_bytes += align_up(n, 64);
         c2o[p] = chars_bytes; chars_bytes += align_up(m, 64);
         if (!w16) { po[p] = plane_elems; plane_elems += (size_t)d.strips * d.t4 * (lay ? kGroupInts1 : kGroupInts); }
-        co[p] = code_elems; code_elems += (size_t)d.strips * d.t16 * SR;
+        co[p] = code_elems; code_elems += (size_t)d.strips * d.t16 * SRf;
         if (!twin) {
             d.band_base = bands;
             bands += d.bands;
@@ -220,7 +257,7 @@ int run_fill(gx_context* ctx, const std::vector<std::pair<const uint8_t*, const 
             so[a] = so[b] = skel_elems; skel_elems += (size_t)d.strips * d.skel_stride;
             fo[a] = fo[b] = feed_recs; feed_recs += (size_t)std::max(d.bands - 1, 0) * d.feed_stride * 2;
             gofs[a] = gofs[b] = prog_elems; prog_elems += (size_t)std::max(d.bands - 1, 0) * kProgStride;
-            if (w16) { po[a] = po[b] = plane_elems; plane_elems += (size_t)d.strips * d.t4 * kTwinGroupBytes; }
+            if (w16) { po[a] = po[b] = plane_elems; plane_elems += (size_t)d.strips * d.t4 * w12_group_bytes(rows); }
         }
     job.total_bands = bands;
     job.total_strips = strips;
@@ -412,8 +449,8 @@ int run_fill(gx_context* ctx, const std::vector<std::pair<const uint8_t*, const 
     const int per_cu = (twin && !getenv("GX_FILL_GRID")) ? std::max(1, 16 / (Wf + 1)) : 1;
     const int grid = std::min(bands, fill_grid_cap(ctx->device) * per_cu);
     if (const char* lg = getenv("GX_LOG"); lg && !strcmp(lg, "debug"))
-        fprintf(stderr, "[gx DEBUG] fill launch: P=%zu layout=%d W=%d twin=%d plane_bytes=%d tbl=%d grid=%d bands=%d\n", P,
-                lay, Wf, twin ? 1 : 0, ctx->last_pbytes, (twin ? twin_tbl : tbl) ? 1 : 0, grid, bands);
+        fprintf(stderr, "[gx DEBUG] fill launch: P=%zu layout=%d W=%d twin=%d rows=%d plane_bytes=%d tbl=%d grid=%d bands=%d\n", P,
+                lay, Wf, twin ? 1 : 0, twin ? rows : 0, ctx->last_pbytes, (twin ? twin_tbl : tbl) ? 1 : 0, grid, bands);
     const auto h_launch = std::chrono::steady_clock::now();
     hipEvent_t evb = slot >= 0 ? ctx->slots[slot].fb : ctx->ev0, eve = slot >= 0 ? ctx->slots[slot].fe : ctx->ev1;
     if (bands > 0 && lay == 3) {   // the column symbols as int32 for layout 3's lanes (before the timed fill)
@@ -425,7 +462,7 @@ int run_fill(gx_context* ctx, const std::vector<std::pair<const uint8_t*, const 
     if (bands > 0 && twin)
         HIPCHK(launch_fill_pk(Wf, (planes ? (w16 ? 2 : 1) : 0) + (twin_tbl ? 4 : 0) + (job.nocodes ? 8 : 0) +
                                   (job.noskel ? 16 : 0) + (is_local ? 32 : 0),
-                              (const PairDev*)job.pairs.p, (int)P, (int)tw.size(), bands, counter,
+                              rows, (const PairDev*)job.pairs.p, (int)P, (int)tw.size(), bands, counter,
                               (PairRes*)job.pres.p, (StripRes*)job.sres.p, scl, grid, fs));
     else if (bands > 0 && lay == 3)
         HIPCHK(launch_fill_skew(W, is_local != 0, planes, tbl, trace.p != nullptr, track, (const PairDev*)job.pairs.p, (int)P,
@@ -665,7 +702,8 @@ hipError_t enqueue_plane_sums(gx_context* ctx, const FillJob& job, const Scores3
     for (const PairDev& d : job.pd) max_strips = std::max(max_strips, d.strips);
     return launch_plane_sums((const PairDev*)job.pairs.p, (int)job.pd.size(), max_strips, job.lay,
                              job.w16 ? 3 : job.d8 ? 2 : 1,
-                             sc.h, sc.g, sc.floor_, (job.shift || job.w16) ? sc.g : 0, out, st ? st : ctx->stream);
+                             sc.h, sc.g, sc.floor_, (job.shift || job.w16) ? sc.g : 0, out,
+                             job.twin ? job.rows : kRowsPerLane, st ? st : ctx->stream);
 }
 
 KeptFill::~KeptFill() { job_release(ctx, job); }

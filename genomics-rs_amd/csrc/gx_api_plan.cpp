@@ -338,15 +338,22 @@ static long long twin_const(const Scores32& sc, bool local) {
     return 2 * (std::llabs(a) + std::llabs(smax) + std::llabs(smin)) + 64 +
            (local ? std::max(0LL, -smin) + std::llabs(g) : 0);
 }
-long long twin_bound(const Scores32& sc, int W, long long dm, bool local) {
-    return twin_step(sc, local) * (192LL * W + 16 + dm) + twin_const(sc, local);
+// Strip height: a lane owns `rows` rows (2, or 4 for the batch fill's 256-row
+// strips), a strip 64 rows of them.  Strip k's lowest row lies 64 rows (k + 1)
+// rows below the band's top row, and its base column (the block it consumes:
+// one lane = one column of lag per lane, whatever the rows per lane) up to
+// 64 (k + 1) + 16 (+ dm) columns to the right: (64 rows + 64)(k + 1) + 16 + dm
+// neighbour steps in all -- 192 (k + 1) at two rows a lane, 320 (k + 1) at four.
+static long long twin_span(int W, long long dm, int rows) { return (64LL * rows + 64) * W + 16 + dm; }
+long long twin_bound(const Scores32& sc, int W, long long dm, bool local, int rows) {
+    return twin_step(sc, local) * twin_span(W, dm, rows) + twin_const(sc, local);
 }
 // Largest column gap between twins that keeps band width W admissible under
 // twin_width's bound (capped at 1,024): twin_table pairs no wider gaps, so one
 // ill-matched twin never narrows the band width of a whole batch.
-long long twin_gap_cap(const Scores32& sc, int W, bool local) {
+long long twin_gap_cap(const Scores32& sc, int W, bool local, int rows) {
     const long long rest = kTwinBoundLimit - 1 - twin_const(sc, local);
-    return std::max(0LL, std::min(1024LL, rest / twin_step(sc, local) - 192LL * W - 16));
+    return std::max(0LL, std::min(1024LL, rest / twin_step(sc, local) - twin_span(W, 0, rows)));
 }
 std::vector<std::pair<int, int>> twin_table(const std::vector<PairHost>& ph, long long gap_cap) {
     std::vector<int> idx(ph.size());
@@ -380,8 +387,10 @@ std::vector<std::pair<int, int>> twin_table(const std::vector<PairHost>& ph, lon
 // sequential walk): long_ok.
 int twin_width(const std::vector<PairHost>& ph, const std::vector<std::pair<int, int>>& tw, const Scores32& sc,
                int is_local, bool track, bool lcs, int lay, bool planes, bool d8, int W_want,
-               bool long_ok) {
+               bool long_ok, int rows) {
     if (const char* e = getenv("GX_TWIN"); e && !strcmp(e, "0")) return 0;
+    // four rows a lane: the global fill with twin codes and no skeleton only (gx_fill_pk.hip R)
+    if (rows != kRowsPerLane && !(rows == kTwinRowsMax && !is_local && long_ok)) return 0;
     if (lay != 0 || track || lcs || (planes && !d8) || sc.g > 0 || sc.h > 0) return 0;
     if (ph.empty()) return 0;
     if (is_local && (!planes || !long_ok)) return 0;
@@ -395,9 +404,34 @@ int twin_width(const std::vector<PairHost>& ph, const std::vector<std::pair<int,
     }
     for (int W : {15, 8, 7, 4, 3}) {
         if (W > W_want && W != 3) continue;
-        if (twin_bound(sc, W, dm, is_local != 0) < kTwinBoundLimit) return W;
+        if (twin_bound(sc, W, dm, is_local != 0, rows) < kTwinBoundLimit) return W;
     }
     return 0;
+}
+
+// Four rows a lane (256-row strips) for the global batch fill with twin codes
+// (run_fill): which launches take it unasked, and their band width.
+// min_strips4 / twin_strips4: the shortest pair's and all twins' 256-row strips.
+// Measured on one lease, two rows against four (GCUPS of the bench line,
+// profiles/r07_rows4_sweep.txt): 80 x 30k 2,905 -> 3,272; 1024 x 16k 2,776 ->
+// 3,347; 1024 x 8k 2,864 -> 3,218; 1024 x 4k 2,539 -> 2,900; 1024 x 2k 1,950 ->
+// 2,257, each at 8-strip bands, one workgroup a CU.  7-strip bands two a CU,
+// the two-row fill's best, lose at four rows wherever the taller bands no
+// longer outnumber the workgroups (the headline: 340 bands a launch on 512
+// workgroups, 2,706; 4 x 3 a CU 3,071, 3 x 4 2,831) and never win (16k 2,790,
+// 8k 3,194, 4k 2,611).  All-vs-all with planes (45 pairs of ~30k, ~170
+// 8-strip bands a launch on 256 CUs) loses 1-3 % (2,467 / 2,552 -> 2,451 /
+// 2,463): four rows only where the launch has at least one 8-strip band of
+// 256-row strips per CU, and pairs of at least 8 such strips (2,048 rows;
+// nothing shorter was measured).
+bool twin_rows4_auto(int min_strips4, int twin_strips4, int grid_cap) {
+    return min_strips4 >= 8 && ceil_div(twin_strips4, 8) >= grid_cap;
+}
+// ... at most 8-strip bands (wider ones were not measured at four rows; the
+// admission bound refuses 15 at the default scores anyway); a forced launch
+// (GX_TWIN_ROWS=4) of a short queue takes the usual narrower widths.
+int twin_rows4_band_waves(int twin_strips4, int grid_cap, int min_strips4) {
+    return std::min(8, fill_band_waves(false, twin_strips4, grid_cap, 0, min_strips4));
 }
 
 // ---------------------------------------------------------------------------
@@ -509,6 +543,19 @@ extern "C" int gx_twin_admission_mode(const gx_scores* scores, int is_local, int
     if (check_scores(scores, 1, 1, &hs, &sc, is_local, nullptr) != GX_OK) return -1;
     const long long b = twin_bound(sc, band_waves, col_gap, is_local != 0);
     if (bound) *bound = b;
+    return (sc.g <= 0 && sc.h <= 0 && b < kTwinBoundLimit) ? 1 : 0;
+}
+
+extern "C" int gx_twin_admission_rows(const gx_scores* scores, int is_local, int band_waves, int64_t col_gap,
+                                      int rows_per_lane, int64_t* bound) {
+    if (!scores || band_waves < 1 || col_gap < 0) return -1;
+    if (rows_per_lane != kRowsPerLane && rows_per_lane != kTwinRowsMax) return -1;
+    HostScores hs;
+    Scores32 sc;
+    if (check_scores(scores, 1, 1, &hs, &sc, is_local, nullptr) != GX_OK) return -1;
+    const long long b = twin_bound(sc, band_waves, col_gap, is_local != 0, rows_per_lane);
+    if (bound) *bound = b;
+    if (rows_per_lane != kRowsPerLane && is_local) return 0;   // local fills keep two rows a lane
     return (sc.g <= 0 && sc.h <= 0 && b < kTwinBoundLimit) ? 1 : 0;
 }
 

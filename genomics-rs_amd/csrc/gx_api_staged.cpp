@@ -295,6 +295,7 @@ extern "C" int gx_staged_table(gx_context* ctx, size_t pair, gx_table** table_ou
     FillJob& j = t->job;
     const FillJob& kj = k->job;
     j.lay = kj.lay; j.W = kj.W; j.planes_on = kj.planes_on; j.d8 = kj.d8; j.shift = kj.shift; j.twin = kj.twin;
+    j.rows = kj.rows;
     j.w16 = kj.w16; j.nocodes = kj.nocodes; j.noskel = kj.noskel; j.local_on = kj.local_on; j.g = kj.g;
     j.fill_ms = kj.fill_ms; j.table = true;
     const int q = k->dev_of[pair];
@@ -343,6 +344,7 @@ extern "C" int gx_staged_steps(const gx_context* ctx, size_t pair, gx_step* step
 
 extern "C" int gx_batch_chunks(const gx_context* ctx) { return ctx ? ctx->last_chunks : -1; }
 extern "C" int gx_fill_twin(const gx_context* ctx) { return ctx ? ctx->last_twin : -1; }
+extern "C" int gx_fill_rows(const gx_context* ctx) { return ctx ? ctx->last_rows : -1; }
 extern "C" int gx_fill_groups(const gx_context* ctx) { return ctx ? ctx->last_groups : -1; }
 extern "C" int gx_fill_plane_bits(const gx_context* ctx) { return ctx ? ctx->last_pbits : -1; }
 

@@ -90,7 +90,7 @@ static int fetch_rows32(const gx_table* t, int which, size_t row0, size_t rows, 
     hipError_t e;
     if (t->job.w16)   // twin plane codes (staged tables): this pair's half of the twin's code plane
         e = launch_export_w16((const uint8_t*)d.pI, d.twin_half, which, (int32_t*)tmp.p, (int)n, (int)m, d.t4,
-                              t->sc.h, t->sc.g, t->sc.floor_, t->sc.g, (int)row0, (int)rows, ctx->stream);
+                              t->sc.h, t->sc.g, t->sc.floor_, t->sc.g, (int)row0, (int)rows, d.rows, ctx->stream);
     else if (t->job.d8)   // compact planes: rebuilt from the insert plane's running sum (+ this plane's x)
         e = launch_export_d8((const uint8_t*)d.pI, which == 0 ? nullptr : (const uint8_t*)src, (int32_t*)tmp.p,
                              (int)n, (int)m, d.t4, t->sc.h, t->sc.g, t->sc.floor_, t->job.shift ? t->sc.g : 0,

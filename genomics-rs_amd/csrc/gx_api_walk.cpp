@@ -159,7 +159,7 @@ int run_traceback(gx_context* ctx, const std::vector<const FillJob*>& jv, const 
     DevBuf tbb, jb;
     int rc;
     auto cleanup = [&]() { pool_put(ctx, tbb); pool_put(ctx, jb); };
-    const int SR = strip_rows(job.lay);
+    const int SR = job_strip_rows(job);
     const size_t nc = 4 * P, nsg = 4 * std::max<size_t>(stot, 1), nhr = std::max<size_t>(stot, 1) * SR;
     if ((rc = pool_get(ctx, (nc + nsg) * sizeof(int) + nhr * sizeof(uint32_t), &tbb, ts)) ||
         (slot < 0 && (rc = pool_get(ctx, P * sizeof(TbDev), &jb, ts)))) {

@@ -371,10 +371,17 @@ __device__ __forceinline__ uint4 w12_load(const uint8_t* rec) {
     const __attribute__((address_space(1))) uint32_t* p = (const __attribute__((address_space(1))) uint32_t*)rec;
     return w12_unpack(p[0], p[1], p[2]);   // (one global_load_dwordx3)
 }
-// Byte offset of the record of row-in-strip rho (lane rho / 2, row-in-lane
-// rho % 2) in 4-step group G of strip s, for strips of t4 groups.
-__device__ __forceinline__ size_t w12_rec_off(const int s, const int t4, const int G, const int rho) {
-    return ((size_t)s * t4 + G) * kTwinGroupBytes + (size_t)(rho & 1) * (kTwinGroupBytes / 2) + (size_t)(rho >> 1) * kTwinRec;
+// Byte offset of the record of row-in-strip rho (lane rho / R, row-in-lane
+// rho % R) in 4-step group G of strip s, for strips of t4 groups filled with
+// R = 2 or 4 rows a lane (64 R-row strips; groups w12_group_bytes(R) apart).
+// Every decoder of the code plane addresses it through this rule.
+__device__ __forceinline__ size_t w12_rec_off(const int s, const int t4, const int G, const int rho, const int R) {
+    const int sh = R == 4 ? 2 : 1;
+    return ((size_t)s * t4 + G) * (size_t)w12_group_bytes(R) + (size_t)(rho & (R - 1)) * (kWave * kTwinRec) +
+           (size_t)(rho >> sh) * kTwinRec;
 }
+// Rows per lane of a pair descriptor (PairDev.rows; 0 from launches that
+// predate the field or never set it: two).
+__device__ __forceinline__ int twin_rows_of(const int rows) { return rows == 4 ? 4 : kRowsPerLane; }
 
 }  // namespace gx

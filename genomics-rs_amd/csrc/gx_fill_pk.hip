@@ -184,8 +184,11 @@ struct RowPk {
     uint32_t E, Etl;                 // landing columns (int16 per half)
     uint32_t lb;                     // local: the largest score_max along the row (biased)
 };
+// R rows a lane (2, or 4 for the batch fill's 256-row strips): rows R l + 1 ..
+// R l + R of the strip, r[0] the topmost
+template <int R>
 struct LanePk {
-    RowPk a, b;
+    RowPk r[R];
     uint32_t c2c;                    // s2[j-1] of both pairs (bytes in the halves)
 };
 
@@ -264,42 +267,48 @@ __device__ __forceinline__ void cell_pk(RowPk& st, const uint32_t dd_in, const u
     if (!NOE) st.Etl = e_up;
 }
 
-template <bool MASKED, bool TBL, bool CODES, bool NOE = false, bool LOCAL = false>
-__device__ __forceinline__ void dp_step_pk(LanePk& st, const Rec& r, const int t, const int lane, const int m0,
-                                           const int m1, const uint32_t c1a, const uint32_t c1b, const uint32_t c1ah,
-                                           const uint32_t c1bh, const PkScores& k,
-                                           uint32_t (&oI)[2], uint32_t (&oD)[2], uint32_t (&oS)[2],
-                                           uint32_t (&oL)[2]) {
-    const uint32_t dd_in = (uint32_t)shr1(r.dd, (int)st.b.Dd);
-    const uint32_t sm_in = (uint32_t)shr1(r.sm, (int)st.b.SMp);
+// One step of a lane: its R cells of one column, top row first; row k takes
+// the delete successor and score_max of row k - 1 (row 0: of the lane above's
+// last row, a step earlier, through the DPP shift; lane 0: the ring record).
+template <bool MASKED, bool TBL, bool CODES, bool NOE, bool LOCAL, int R>
+__device__ __forceinline__ void dp_step_pk(LanePk<R>& st, const Rec& r, const int t, const int lane, const int m0,
+                                           const int m1, const uint32_t (&c1)[R], const uint32_t (&c1h)[R],
+                                           const PkScores& k,
+                                           uint32_t (&oI)[R], uint32_t (&oD)[R], uint32_t (&oS)[R],
+                                           uint32_t (&oL)[R]) {
+    const uint32_t dd_in = (uint32_t)shr1(r.dd, (int)st.r[R - 1].Dd);
+    const uint32_t sm_in = (uint32_t)shr1(r.sm, (int)st.r[R - 1].SMp);
     const uint32_t c2 = (uint32_t)shr1(r.c2, (int)st.c2c);
-    const uint32_t e_in = NOE ? 0u : (uint32_t)shr1((int)pk2(t + 1, t + 1), (int)st.b.E);   // lane 0: its own column
+    const uint32_t e_in = NOE ? 0u : (uint32_t)shr1((int)pk2(t + 1, t + 1), (int)st.r[R - 1].E);   // lane 0: its own column
     const uint32_t act = MASKED ? ((unsigned)(t - lane) < (unsigned)m0 ? 0xFFFFu : 0u) |
                                       ((unsigned)(t - lane) < (unsigned)m1 ? 0xFFFF0000u : 0u)
                                 : ~0u;
-    cell_pk<MASKED, TBL, CODES, NOE, LOCAL>(st.a, dd_in, sm_in, e_in, c2, c1a, c1ah, act, k, oI[0], oD[0], oS[0], oL[0]);
-    cell_pk<MASKED, TBL, CODES, NOE, LOCAL>(st.b, st.a.Dd, st.a.SMp, st.a.E, c2, c1b, c1bh, act, k, oI[1], oD[1], oS[1], oL[1]);
+    cell_pk<MASKED, TBL, CODES, NOE, LOCAL>(st.r[0], dd_in, sm_in, e_in, c2, c1[0], c1h[0], act, k, oI[0], oD[0], oS[0], oL[0]);
+#pragma unroll
+    for (int q = 1; q < R; ++q)
+        cell_pk<MASKED, TBL, CODES, NOE, LOCAL>(st.r[q], st.r[q - 1].Dd, st.r[q - 1].SMp, st.r[q - 1].E, c2, c1[q], c1h[q], act,
+                                                k, oI[q], oD[q], oS[q], oL[q]);
     st.c2c = c2;
 }
 
-template <int U>
-__device__ __forceinline__ void push63_pk(uint32_t base, const LanePk& st, unsigned long long m63) {
+template <int U, int R>
+__device__ __forceinline__ void push63_pk(uint32_t base, const LanePk<R>& st, unsigned long long m63) {
     asm volatile(
         "s_mov_b64 exec, %0\n\t"
         "ds_write2_b32 %1, %2, %3 offset0:%5 offset1:%6\n\t"
         "ds_write_b32 %1, %4 offset:%7\n\t"
         "s_mov_b64 exec, -1"
         :
-        : "s"(m63), "v"(base), "v"(st.b.Dd), "v"(st.b.SMp), "v"(st.c2c), "i"(4 * U), "i"(4 * U + 1), "i"(16 * U + 8)
+        : "s"(m63), "v"(base), "v"(st.r[R - 1].Dd), "v"(st.r[R - 1].SMp), "v"(st.c2c), "i"(4 * U), "i"(4 * U + 1), "i"(16 * U + 8)
         : "memory");
 }
-template <int U>
-__device__ __forceinline__ void push_all_pk(uint32_t vaddr, const LanePk& st) {
+template <int U, int R>
+__device__ __forceinline__ void push_all_pk(uint32_t vaddr, const LanePk<R>& st) {
     asm volatile(
         "ds_write2_b32 %0, %1, %2 offset0:%4 offset1:%5\n\t"
         "ds_write_b32 %0, %3 offset:%6"
         :
-        : "v"(vaddr), "v"(st.b.Dd), "v"(st.b.SMp), "v"(st.c2c), "i"(4 * U), "i"(4 * U + 1), "i"(16 * U + 8)
+        : "v"(vaddr), "v"(st.r[R - 1].Dd), "v"(st.r[R - 1].SMp), "v"(st.c2c), "i"(4 * U), "i"(4 * U + 1), "i"(16 * U + 8)
         : "memory");
 }
 
@@ -324,6 +333,7 @@ __device__ __forceinline__ void read4_pk(Rec (&r)[4], const Rec* rin) {
 constexpr int kBaseSlots = 32;
 // (as lds_int pairs: slot k = ints 2k, 2k + 1)
 
+template <int R>
 struct WavePk {
     uint8_t* pI[2]; uint8_t* pD[2]; uint8_t* pS[2];   // this strip's compact planes, per pair
     uint32_t* codes[2];
@@ -339,13 +349,21 @@ struct WavePk {
     uint32_t cnt_addr;
     int m, lane;                                      // m: the twin's columns (the longer pair's)
     int m0, m1;                                       // each pair's own columns
-    uint32_t c1a, c1b;                                // rows A, B: both pairs' chars (TBL: pair 0's penalty tables)
-    uint32_t c1ah, c1bh;                              // TBL: pair 1's penalty tables
+    uint32_t c1[R];                                   // the rows' chars of both pairs (TBL: pair 0's penalty tables)
+    uint32_t c1h[R];                                  // TBL: pair 1's penalty tables
     int B0, B1;                                       // current bases (wave-uniform)
 };
 
-template <int PLANES, bool MASKED, int G4>
-__device__ __forceinline__ void group4_pk(LanePk& st, Rec (&nxt)[4], WavePk& w, const PkScores& k, const int t0,
+// Step U's twin plane codes, every row of the lane.
+template <int U, int R>
+__device__ __forceinline__ void codes_step_pk(uint32_t (&wc)[R][4], const uint32_t (&oI)[R], const uint32_t (&oD)[R],
+                                              const uint32_t (&oS)[R], const uint32_t (&oL)[R]) {
+#pragma unroll
+    for (int q = 0; q < R; ++q) wc[q][U] = w16_code(oI[q], oD[q], oS[q], oL[q]);
+}
+
+template <int PLANES, bool MASKED, int G4, int R>
+__device__ __forceinline__ void group4_pk(LanePk<R>& st, Rec (&nxt)[4], WavePk<R>& w, const PkScores& k, const int t0,
                                           const uint32_t out_base, const bool push_on, const size_t sb_off) {
     const int t = t0 + 4 * G4;
     Rec cur[4] = {nxt[0], nxt[1], nxt[2], nxt[3]};
@@ -353,74 +371,70 @@ __device__ __forceinline__ void group4_pk(LanePk& st, Rec (&nxt)[4], WavePk& w, 
     const int seen_v = *w.wcnt_in;
     asm volatile("" ::: "memory");
     read4_pk(nxt, w.ring_in + ring_slot(t + 5));
-    uint32_t bI[4][2], bD[4][2], bS[4][2], bL[4][2];
+    static_assert(R == 2 || (PLANES & 3) != 1, "byte planes: two rows a lane");
+    uint32_t bI[4][R], bD[4][R], bS[4][R], bL[4][R];
     uint32_t xI[2][2], xS[2][2], xD[2][2];   // compact plane dwords [pair][row], filled step by step (PLANES 1)
-    uint32_t wc[2][4];                        // twin plane codes [row][step] (PLANES 2)
+    uint32_t wc[R][4];                        // twin plane codes [row][step] (PLANES 2)
     const int col0 = t - (kWave - 1);
     if (MASKED) {
         auto sko = [&](int c) { return (c >= 0 && c <= w.m) ? w.skel_voff + 4u * (uint32_t)c : kSkelOff; };
         push63_pk<4 * G4 + 0>(out_base, st, lane63_mask(push_on && col0 >= 0 && col0 <= w.m));
-        dp_step_pk<true, (PLANES & 4) != 0, (PLANES & 8) == 0, (PLANES & 16) != 0, (PLANES & 32) != 0>(st, cur[0], t + 0, w.lane, w.m0, w.m1, w.c1a, w.c1b, w.c1ah, w.c1bh, k, bI[0], bD[0], bS[0], bL[0]);
-        if ((PLANES & 3) == 1) bytes_step<0>(xI, xS, xD, bI[0], bD[0], bS[0], bL[0]);
-        if ((PLANES & 3) == 2) { wc[0][0] = w16_code(bI[0][0], bD[0][0], bS[0][0], bL[0][0]);
-                           wc[1][0] = w16_code(bI[0][1], bD[0][1], bS[0][1], bL[0][1]); }
-        if ((PLANES & 16) == 0) skel_store(w.skel_rsrc, sko(col0 + 1), (int)st.b.E);
+        dp_step_pk<true, (PLANES & 4) != 0, (PLANES & 8) == 0, (PLANES & 16) != 0, (PLANES & 32) != 0, R>(st, cur[0], t + 0, w.lane, w.m0, w.m1, w.c1, w.c1h, k, bI[0], bD[0], bS[0], bL[0]);
+        if constexpr ((PLANES & 3) == 1) bytes_step<0>(xI, xS, xD, bI[0], bD[0], bS[0], bL[0]);
+        if ((PLANES & 3) == 2) codes_step_pk<0, R>(wc, bI[0], bD[0], bS[0], bL[0]);
+        if ((PLANES & 16) == 0) skel_store(w.skel_rsrc, sko(col0 + 1), (int)st.r[R - 1].E);
         push63_pk<4 * G4 + 1>(out_base, st, lane63_mask(push_on && col0 + 1 >= 0 && col0 + 1 <= w.m));
-        dp_step_pk<true, (PLANES & 4) != 0, (PLANES & 8) == 0, (PLANES & 16) != 0, (PLANES & 32) != 0>(st, cur[1], t + 1, w.lane, w.m0, w.m1, w.c1a, w.c1b, w.c1ah, w.c1bh, k, bI[1], bD[1], bS[1], bL[1]);
-        if ((PLANES & 3) == 1) bytes_step<1>(xI, xS, xD, bI[1], bD[1], bS[1], bL[1]);
-        if ((PLANES & 3) == 2) { wc[0][1] = w16_code(bI[1][0], bD[1][0], bS[1][0], bL[1][0]);
-                           wc[1][1] = w16_code(bI[1][1], bD[1][1], bS[1][1], bL[1][1]); }
-        if ((PLANES & 16) == 0) skel_store(w.skel_rsrc, sko(col0 + 2), (int)st.b.E);
+        dp_step_pk<true, (PLANES & 4) != 0, (PLANES & 8) == 0, (PLANES & 16) != 0, (PLANES & 32) != 0, R>(st, cur[1], t + 1, w.lane, w.m0, w.m1, w.c1, w.c1h, k, bI[1], bD[1], bS[1], bL[1]);
+        if constexpr ((PLANES & 3) == 1) bytes_step<1>(xI, xS, xD, bI[1], bD[1], bS[1], bL[1]);
+        if ((PLANES & 3) == 2) codes_step_pk<1, R>(wc, bI[1], bD[1], bS[1], bL[1]);
+        if ((PLANES & 16) == 0) skel_store(w.skel_rsrc, sko(col0 + 2), (int)st.r[R - 1].E);
         push63_pk<4 * G4 + 2>(out_base, st, lane63_mask(push_on && col0 + 2 >= 0 && col0 + 2 <= w.m));
-        dp_step_pk<true, (PLANES & 4) != 0, (PLANES & 8) == 0, (PLANES & 16) != 0, (PLANES & 32) != 0>(st, cur[2], t + 2, w.lane, w.m0, w.m1, w.c1a, w.c1b, w.c1ah, w.c1bh, k, bI[2], bD[2], bS[2], bL[2]);
-        if ((PLANES & 3) == 1) bytes_step<2>(xI, xS, xD, bI[2], bD[2], bS[2], bL[2]);
-        if ((PLANES & 3) == 2) { wc[0][2] = w16_code(bI[2][0], bD[2][0], bS[2][0], bL[2][0]);
-                           wc[1][2] = w16_code(bI[2][1], bD[2][1], bS[2][1], bL[2][1]); }
-        if ((PLANES & 16) == 0) skel_store(w.skel_rsrc, sko(col0 + 3), (int)st.b.E);
+        dp_step_pk<true, (PLANES & 4) != 0, (PLANES & 8) == 0, (PLANES & 16) != 0, (PLANES & 32) != 0, R>(st, cur[2], t + 2, w.lane, w.m0, w.m1, w.c1, w.c1h, k, bI[2], bD[2], bS[2], bL[2]);
+        if constexpr ((PLANES & 3) == 1) bytes_step<2>(xI, xS, xD, bI[2], bD[2], bS[2], bL[2]);
+        if ((PLANES & 3) == 2) codes_step_pk<2, R>(wc, bI[2], bD[2], bS[2], bL[2]);
+        if ((PLANES & 16) == 0) skel_store(w.skel_rsrc, sko(col0 + 3), (int)st.r[R - 1].E);
         push63_pk<4 * G4 + 3>(out_base, st, lane63_mask(push_on && col0 + 3 >= 0 && col0 + 3 <= w.m));
         if (push_on && col0 + 3 >= 0 && col0 <= w.m) lds_store_lane0(w.wcnt_out, min(col0 + 3, w.m) + 1);
-        dp_step_pk<true, (PLANES & 4) != 0, (PLANES & 8) == 0, (PLANES & 16) != 0, (PLANES & 32) != 0>(st, cur[3], t + 3, w.lane, w.m0, w.m1, w.c1a, w.c1b, w.c1ah, w.c1bh, k, bI[3], bD[3], bS[3], bL[3]);
-        if ((PLANES & 3) == 1) bytes_step<3>(xI, xS, xD, bI[3], bD[3], bS[3], bL[3]);
-        if ((PLANES & 3) == 2) { wc[0][3] = w16_code(bI[3][0], bD[3][0], bS[3][0], bL[3][0]);
-                           wc[1][3] = w16_code(bI[3][1], bD[3][1], bS[3][1], bL[3][1]); }
-        if ((PLANES & 16) == 0) skel_store(w.skel_rsrc, sko(col0 + 4), (int)st.b.E);
+        dp_step_pk<true, (PLANES & 4) != 0, (PLANES & 8) == 0, (PLANES & 16) != 0, (PLANES & 32) != 0, R>(st, cur[3], t + 3, w.lane, w.m0, w.m1, w.c1, w.c1h, k, bI[3], bD[3], bS[3], bL[3]);
+        if constexpr ((PLANES & 3) == 1) bytes_step<3>(xI, xS, xD, bI[3], bD[3], bS[3], bL[3]);
+        if ((PLANES & 3) == 2) codes_step_pk<3, R>(wc, bI[3], bD[3], bS[3], bL[3]);
+        if ((PLANES & 16) == 0) skel_store(w.skel_rsrc, sko(col0 + 4), (int)st.r[R - 1].E);
     } else {
         const uint32_t pa = push_on && w.lane == kWave - 1 ? out_base : w.scratch;
         push_all_pk<4 * G4 + 0>(pa, st);
-        dp_step_pk<false, (PLANES & 4) != 0, (PLANES & 8) == 0, (PLANES & 16) != 0, (PLANES & 32) != 0>(st, cur[0], t + 0, w.lane, w.m0, w.m1, w.c1a, w.c1b, w.c1ah, w.c1bh, k, bI[0], bD[0], bS[0], bL[0]);
-        if ((PLANES & 3) == 1) bytes_step<0>(xI, xS, xD, bI[0], bD[0], bS[0], bL[0]);
-        if ((PLANES & 3) == 2) { wc[0][0] = w16_code(bI[0][0], bD[0][0], bS[0][0], bL[0][0]);
-                           wc[1][0] = w16_code(bI[0][1], bD[0][1], bS[0][1], bL[0][1]); }
-        const uint32_t e0 = st.b.E;
+        dp_step_pk<false, (PLANES & 4) != 0, (PLANES & 8) == 0, (PLANES & 16) != 0, (PLANES & 32) != 0, R>(st, cur[0], t + 0, w.lane, w.m0, w.m1, w.c1, w.c1h, k, bI[0], bD[0], bS[0], bL[0]);
+        if constexpr ((PLANES & 3) == 1) bytes_step<0>(xI, xS, xD, bI[0], bD[0], bS[0], bL[0]);
+        if ((PLANES & 3) == 2) codes_step_pk<0, R>(wc, bI[0], bD[0], bS[0], bL[0]);
+        const uint32_t e0 = st.r[R - 1].E;
         push_all_pk<4 * G4 + 1>(pa, st);
-        dp_step_pk<false, (PLANES & 4) != 0, (PLANES & 8) == 0, (PLANES & 16) != 0, (PLANES & 32) != 0>(st, cur[1], t + 1, w.lane, w.m0, w.m1, w.c1a, w.c1b, w.c1ah, w.c1bh, k, bI[1], bD[1], bS[1], bL[1]);
-        if ((PLANES & 3) == 1) bytes_step<1>(xI, xS, xD, bI[1], bD[1], bS[1], bL[1]);
-        if ((PLANES & 3) == 2) { wc[0][1] = w16_code(bI[1][0], bD[1][0], bS[1][0], bL[1][0]);
-                           wc[1][1] = w16_code(bI[1][1], bD[1][1], bS[1][1], bL[1][1]); }
-        const uint32_t e1 = st.b.E;
+        dp_step_pk<false, (PLANES & 4) != 0, (PLANES & 8) == 0, (PLANES & 16) != 0, (PLANES & 32) != 0, R>(st, cur[1], t + 1, w.lane, w.m0, w.m1, w.c1, w.c1h, k, bI[1], bD[1], bS[1], bL[1]);
+        if constexpr ((PLANES & 3) == 1) bytes_step<1>(xI, xS, xD, bI[1], bD[1], bS[1], bL[1]);
+        if ((PLANES & 3) == 2) codes_step_pk<1, R>(wc, bI[1], bD[1], bS[1], bL[1]);
+        const uint32_t e1 = st.r[R - 1].E;
         push_all_pk<4 * G4 + 2>(pa, st);
-        dp_step_pk<false, (PLANES & 4) != 0, (PLANES & 8) == 0, (PLANES & 16) != 0, (PLANES & 32) != 0>(st, cur[2], t + 2, w.lane, w.m0, w.m1, w.c1a, w.c1b, w.c1ah, w.c1bh, k, bI[2], bD[2], bS[2], bL[2]);
-        if ((PLANES & 3) == 1) bytes_step<2>(xI, xS, xD, bI[2], bD[2], bS[2], bL[2]);
-        if ((PLANES & 3) == 2) { wc[0][2] = w16_code(bI[2][0], bD[2][0], bS[2][0], bL[2][0]);
-                           wc[1][2] = w16_code(bI[2][1], bD[2][1], bS[2][1], bL[2][1]); }
-        const uint32_t e2 = st.b.E;
+        dp_step_pk<false, (PLANES & 4) != 0, (PLANES & 8) == 0, (PLANES & 16) != 0, (PLANES & 32) != 0, R>(st, cur[2], t + 2, w.lane, w.m0, w.m1, w.c1, w.c1h, k, bI[2], bD[2], bS[2], bL[2]);
+        if constexpr ((PLANES & 3) == 1) bytes_step<2>(xI, xS, xD, bI[2], bD[2], bS[2], bL[2]);
+        if ((PLANES & 3) == 2) codes_step_pk<2, R>(wc, bI[2], bD[2], bS[2], bL[2]);
+        const uint32_t e2 = st.r[R - 1].E;
         push_all_pk<4 * G4 + 3>(pa, st);
         publish_all(w.cnt_addr, col0 + 3 + 1);
-        dp_step_pk<false, (PLANES & 4) != 0, (PLANES & 8) == 0, (PLANES & 16) != 0, (PLANES & 32) != 0>(st, cur[3], t + 3, w.lane, w.m0, w.m1, w.c1a, w.c1b, w.c1ah, w.c1bh, k, bI[3], bD[3], bS[3], bL[3]);
-        if ((PLANES & 3) == 1) bytes_step<3>(xI, xS, xD, bI[3], bD[3], bS[3], bL[3]);
-        if ((PLANES & 3) == 2) { wc[0][3] = w16_code(bI[3][0], bD[3][0], bS[3][0], bL[3][0]);
-                           wc[1][3] = w16_code(bI[3][1], bD[3][1], bS[3][1], bL[3][1]); }
+        dp_step_pk<false, (PLANES & 4) != 0, (PLANES & 8) == 0, (PLANES & 16) != 0, (PLANES & 32) != 0, R>(st, cur[3], t + 3, w.lane, w.m0, w.m1, w.c1, w.c1h, k, bI[3], bD[3], bS[3], bL[3]);
+        if constexpr ((PLANES & 3) == 1) bytes_step<3>(xI, xS, xD, bI[3], bD[3], bS[3], bL[3]);
+        if ((PLANES & 3) == 2) codes_step_pk<3, R>(wc, bI[3], bD[3], bS[3], bL[3]);
         if ((PLANES & 16) == 0)
-            skel_store4(w.skel_rsrc, w.skel_voff + 4u * (uint32_t)(col0 + 1), (int)e0, (int)e1, (int)e2, (int)st.b.E);
+            skel_store4(w.skel_rsrc, w.skel_voff + 4u * (uint32_t)(col0 + 1), (int)e0, (int)e1, (int)e2, (int)st.r[R - 1].E);
     }
     if ((PLANES & 3) == 2) {
-        // twin plane codes: per strip [group][row][lane] 12-B records (1.5 KB a
-        // group; gx_device.h w12_pack), one dwordx3 per row and lane
-        const auto r = rsrc_of(w.pI[0] + sb_off * (kTwinGroupBytes / kGroupInts), 4 * kTwinGroupBytes);
-        const uint32_t v = (uint32_t)G4 * kTwinGroupBytes + (uint32_t)w.lane * kTwinRec;
+        // twin plane codes: per strip [group][row-in-lane][lane] 12-B records (768 B
+        // a row, R rows a group; gx_device.h w12_pack, w12_rec_off), one dwordx3
+        // per row and lane
+        constexpr int kTG = w12_group_bytes(R);
+        static_assert(kTG % kGroupInts == 0, "sb_off counts groups of kGroupInts");
+        const auto r = rsrc_of(w.pI[0] + sb_off * (kTG / kGroupInts), 4 * kTG);
+        const uint32_t v = (uint32_t)G4 * kTG + (uint32_t)w.lane * kTwinRec;
         typedef int v3i __attribute__((ext_vector_type(3)));
 #pragma unroll
-        for (int row = 0; row < 2; ++row) {
+        for (int row = 0; row < R; ++row) {
             uint32_t w0, w1, w2;
 #ifdef GX_DIAG_NO_PACK   // (timing only: the codes computed, neither packed nor stored)
             asm volatile("" ::"v"(wc[row][0]), "v"(wc[row][1]), "v"(wc[row][2]), "v"(wc[row][3]));
@@ -429,7 +443,7 @@ __device__ __forceinline__ void group4_pk(LanePk& st, Rec (&nxt)[4], WavePk& w, 
             w12_pack(wc[row][0], wc[row][1], wc[row][2], wc[row][3], w0, w1, w2);
 #ifndef GX_DIAG_NO_PLANES
             __builtin_amdgcn_raw_buffer_store_b96(v3i{(int)w0, (int)w1, (int)w2}, r,
-                                                  (int)(v + (uint32_t)row * (kTwinGroupBytes / 2)), 0, GX_PLANE_AUX);
+                                                  (int)(v + (uint32_t)row * (kWave * kTwinRec)), 0, GX_PLANE_AUX);
 #else
             asm volatile("" ::"v"(w0), "v"(w1), "v"(w2));
 #endif
@@ -482,18 +496,19 @@ __device__ __forceinline__ void rebase_row(RowPk& r, uint32_t dpk) {
     r.I = psubs(r.I, dpk); r.Hx = psubs(r.Hx, dpk); r.Dd = psubs(r.Dd, dpk);
     r.SMp = psubs(r.SMp, dpk); r.SMtl = psubs(r.SMtl, dpk);
 }
-__device__ __forceinline__ void rebase(LanePk& st, uint32_t dpk) {
-    rebase_row(st.a, dpk);
-    rebase_row(st.b, dpk);
+template <int R>
+__device__ __forceinline__ void rebase(LanePk<R>& st, uint32_t dpk) {
+#pragma unroll
+    for (int q = 0; q < R; ++q) rebase_row(st.r[q], dpk);
 }
 
-template <int PLANES, bool MASKED>
-__device__ __forceinline__ void sub_block_pk(LanePk& st, Rec (&nxt)[4], WavePk& w, const PkScores& k, const int t0,
+template <int PLANES, bool MASKED, int R>
+__device__ __forceinline__ void sub_block_pk(LanePk<R>& st, Rec (&nxt)[4], WavePk<R>& w, const PkScores& k, const int t0,
                                              const uint32_t out_base, const bool push_on, const size_t sb_off) {
-    group4_pk<PLANES, MASKED, 0>(st, nxt, w, k, t0, out_base, push_on, sb_off);
-    group4_pk<PLANES, MASKED, 1>(st, nxt, w, k, t0, out_base, push_on, sb_off);
-    group4_pk<PLANES, MASKED, 2>(st, nxt, w, k, t0, out_base, push_on, sb_off);
-    group4_pk<PLANES, MASKED, 3>(st, nxt, w, k, t0, out_base, push_on, sb_off);
+    group4_pk<PLANES, MASKED, 0, R>(st, nxt, w, k, t0, out_base, push_on, sb_off);
+    group4_pk<PLANES, MASKED, 1, R>(st, nxt, w, k, t0, out_base, push_on, sb_off);
+    group4_pk<PLANES, MASKED, 2, R>(st, nxt, w, k, t0, out_base, push_on, sb_off);
+    group4_pk<PLANES, MASKED, 3, R>(st, nxt, w, k, t0, out_base, push_on, sb_off);
 }
 
 // Initial state of row i (column 0, algo.rs:204-211) in shifted values:
@@ -522,22 +537,24 @@ __device__ __forceinline__ void init_row_pk(RowPk& rs, const Scores32& sc, int B
     rs.cI = 0; rs.cD = 0;
 }
 
-template <int PLANES>
+template <int PLANES, int R>
 __device__ void compute_wave_pk(const PairDev& P0, const PairDev& P1, const int s, const int lane, const Scores32& sc,
                                 const PkScores& k, const Rec* ring_in, Rec* ring_out, lds_int* wcnt_in,
                                 lds_int* rcnt_in, lds_int* wcnt_out, lds_int* rcnt_out, lds_int* base_in,
                                 lds_int* base_out, const bool has_consumer, PairRes* pres0, PairRes* pres1,
                                 int* status, const uint32_t scratch_base, StripRes* sres) {
     constexpr bool LOCAL = (PLANES & 32) != 0;
+    // four rows a lane: the batch fill only (twin codes, no code words, no skeleton, global)
+    static_assert(R == 2 || (R == 4 && (PLANES & 59) == 26), "rows per lane");
     // a twin's pairs may differ in shape: the sweep covers the longer's rows
     // and columns (the host lays both out for that shape); each pair keeps
     // its own characters, column masks and end cell
     const int m = max(P0.m, P1.m), mmin = min(P0.m, P1.m);
-    const int ia = s * kStripRows + kRowsPerLane * lane + 1;
-    WavePk w;
+    const int ia = s * (kWave * R) + R * lane + 1;   // the lane's top row
+    WavePk<R> w;
     {
         // bytes per compact plane per strip (PLANES 2: the twin's one code plane, 1.5 KB a group)
-        const size_t strip_planes = (size_t)s * P0.t4 * ((PLANES & 3) == 2 ? kTwinGroupBytes : kGroupInts);
+        const size_t strip_planes = (size_t)s * P0.t4 * ((PLANES & 3) == 2 ? w12_group_bytes(R) : kGroupInts);
         w.pI[0] = (PLANES & 3) ? (uint8_t*)P0.pI + strip_planes : nullptr;
         w.pD[0] = (PLANES & 3) == 1 ? (uint8_t*)P0.pD + strip_planes : nullptr;
         w.pS[0] = (PLANES & 3) == 1 ? (uint8_t*)P0.pS + strip_planes : nullptr;
@@ -555,15 +572,15 @@ __device__ void compute_wave_pk(const PairDev& P0, const PairDev& P1, const int 
     w.scratch = scratch_base + 4u * (uint32_t)lane;
     w.cnt_addr = (has_consumer && lane == kWave - 1) ? lds_addr((const void*)wcnt_out) : w.scratch;
     w.m = m; w.lane = lane; w.m0 = P0.m; w.m1 = P1.m;
-    if constexpr ((PLANES & 4) != 0) {   // TBL: score tables of rows A, B per pair
-        w.c1a = score_table_pk(ia <= P0.n ? (int)P0.c1[ia - 1] : 0x100, sc);
-        w.c1ah = score_table_pk(ia <= P1.n ? (int)P1.c1[ia - 1] : 0x100, sc);
-        w.c1b = score_table_pk(ia + 1 <= P0.n ? (int)P0.c1[ia] : 0x100, sc);
-        w.c1bh = score_table_pk(ia + 1 <= P1.n ? (int)P1.c1[ia] : 0x100, sc);
-    } else {
-        w.c1a = pk2(ia <= P0.n ? (int)P0.c1[ia - 1] : 0x100, ia <= P1.n ? (int)P1.c1[ia - 1] : 0x100);
-        w.c1b = pk2(ia + 1 <= P0.n ? (int)P0.c1[ia] : 0x100, ia + 1 <= P1.n ? (int)P1.c1[ia] : 0x100);
-        w.c1ah = w.c1bh = 0;
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+        if constexpr ((PLANES & 4) != 0) {   // TBL: the rows' score tables per pair
+            w.c1[q] = score_table_pk(ia + q <= P0.n ? (int)P0.c1[ia + q - 1] : 0x100, sc);
+            w.c1h[q] = score_table_pk(ia + q <= P1.n ? (int)P1.c1[ia + q - 1] : 0x100, sc);
+        } else {
+            w.c1[q] = pk2(ia + q <= P0.n ? (int)P0.c1[ia + q - 1] : 0x100, ia + q <= P1.n ? (int)P1.c1[ia + q - 1] : 0x100);
+            w.c1h[q] = 0;
+        }
     }
 
     // column 0 of the row above: its bases and record (published with the ring's first counter)
@@ -571,18 +588,21 @@ __device__ void compute_wave_pk(const PairDev& P0, const PairDev& P1, const int 
     w.B0 = __builtin_amdgcn_readfirstlane(base_in[0]);   // slot 0: column 0
     w.B1 = __builtin_amdgcn_readfirstlane(base_in[1]);
     PkScores kl = k;                                      // (LOCAL: the floor follows the bases)
-    int lmx[2][2] = {{0, 0}, {0, 0}};                     // LOCAL: rows A, B: absolute row maxima, both pairs
+    int lmx[R][2] = {};                                   // LOCAL: each row's absolute maxima, both pairs
     if (LOCAL) kl.Z = local_floor(w.B0, w.B1);
-    LanePk st;
-    init_row_pk<LOCAL>(st.a, sc, w.B0, w.B1, kl);
-    init_row_pk<LOCAL>(st.b, sc, w.B0, w.B1, kl);
+    LanePk<R> st;
+#pragma unroll
+    for (int q = 0; q < R; ++q) init_row_pk<LOCAL>(st.r[q], sc, w.B0, w.B1, kl);
     st.c2c = 0;
-    st.b.SMtl = st.a.SMp;                                   // (A, 0) is row B's top-left for column 1
-    st.a.E = pk2(-(kRowsPerLane * lane + 1), -(kRowsPerLane * lane + 1));
-    st.b.E = pk2(-(kRowsPerLane * lane + 2), -(kRowsPerLane * lane + 2));
-    st.b.Etl = st.a.E;
+#pragma unroll
+    for (int q = 0; q < R; ++q) st.r[q].E = pk2(-(R * lane + q + 1), -(R * lane + q + 1));
+#pragma unroll
+    for (int q = 1; q < R; ++q) {
+        st.r[q].SMtl = st.r[q - 1].SMp;                     // (row above, 0) is the row's top-left for column 1
+        st.r[q].Etl = st.r[q - 1].E;
+    }
     if (has_consumer) {
-        if (lane == kWave - 1) ring_out[ring_slot(0)] = Rec{(int)st.b.Dd, (int)st.b.SMp, 0, 0};
+        if (lane == kWave - 1) ring_out[ring_slot(0)] = Rec{(int)st.r[R - 1].Dd, (int)st.r[R - 1].SMp, 0, 0};
         if (lane == 0) { base_out[0] = w.B0; base_out[1] = w.B1; }
         lds_wait();
         if (lane == 0) *wcnt_out = 1;
@@ -590,8 +610,8 @@ __device__ void compute_wave_pk(const PairDev& P0, const PairDev& P1, const int 
     Rec nxt[4];
     {
         const Rec r0 = ring_in[ring_slot(0)];
-        st.a.SMtl = (uint32_t)shr1(r0.sm, (int)st.b.SMp);
-        st.a.Etl = (uint32_t)shr1(0, (int)st.b.E);
+        st.r[0].SMtl = (uint32_t)shr1(r0.sm, (int)st.r[R - 1].SMp);
+        st.r[0].Etl = (uint32_t)shr1(0, (int)st.r[R - 1].E);
         read4_pk(nxt, ring_in + ring_slot(1));
     }
     const int T = m + kWave;
@@ -604,7 +624,10 @@ __device__ void compute_wave_pk(const PairDev& P0, const PairDev& P1, const int 
         if (t0 < m) {
             const int2 nb = base_of(base_in, blk);
             if (nb.x != w.B0 || nb.y != w.B1) {
-                if (LOCAL) { fold_lb(st.a, lmx[0], w.B0, w.B1); fold_lb(st.b, lmx[1], w.B0, w.B1); }
+                if (LOCAL) {
+#pragma unroll
+                    for (int q = 0; q < R; ++q) fold_lb(st.r[q], lmx[q], w.B0, w.B1);
+                }
                 rebase(st, pk2(nb.x - w.B0, nb.y - w.B1));
                 w.B0 = nb.x; w.B1 = nb.y;
                 if (LOCAL) kl.Z = local_floor(w.B0, w.B1);
@@ -620,12 +643,13 @@ __device__ void compute_wave_pk(const PairDev& P0, const PairDev& P1, const int 
         const size_t sb_off = (size_t)(t0 >> 2) * kGroupInts;
         const bool full = (t0 >= kWave) && (t0 + kSub - 1 <= mmin - 1);
         const uint32_t out_base = lds_addr(ring_out + ring_slot(t0 - (kWave - 1)));
-        if (full) sub_block_pk<PLANES, false>(st, nxt, w, kl, t0, out_base, has_consumer, sb_off);
-        else sub_block_pk<PLANES, true>(st, nxt, w, kl, t0, out_base, has_consumer, sb_off);
+        if (full) sub_block_pk<PLANES, false, R>(st, nxt, w, kl, t0, out_base, has_consumer, sb_off);
+        else sub_block_pk<PLANES, true, R>(st, nxt, w, kl, t0, out_base, has_consumer, sb_off);
         if constexpr ((PLANES & 8) == 0) {   // code words of both pairs: codes[strip][t/16][lane][row-in-lane]
+            static_assert(R == kRowsPerLane, "code words: two rows a lane");
             typedef unsigned v2u __attribute__((ext_vector_type(2)));
             typedef __attribute__((address_space(1))) v2u gv2u;
-            const uint32_t aI = psub(0, st.a.cI), aD = psub(0, st.a.cD), bI = psub(0, st.b.cI), bD = psub(0, st.b.cD);
+            const uint32_t aI = psub(0, st.r[0].cI), aD = psub(0, st.r[0].cD), bI = psub(0, st.r[1].cI), bD = psub(0, st.r[1].cD);
             const v2u c0 = {(aD << 16) | (aI & 0xFFFFu), (bD << 16) | (bI & 0xFFFFu)};
             const v2u c1 = {(aD & 0xFFFF0000u) | (aI >> 16), (bD & 0xFFFF0000u) | (bI >> 16)};
             const size_t wo = ((size_t)(t0 >> 4) * kWave + lane) * kRowsPerLane;
@@ -639,8 +663,9 @@ __device__ void compute_wave_pk(const PairDev& P0, const PairDev& P1, const int 
         // ties) -> StripRes, which finalize_kernel reduces over the strips;
         // local_col_kernel then finds the row's last column holding it
         // (algo.rs:310-322)
-        fold_lb(st.a, lmx[0], w.B0, w.B1);
-        fold_lb(st.b, lmx[1], w.B0, w.B1);
+        static_assert(!LOCAL || R == kRowsPerLane, "local fill: two rows a lane");
+        fold_lb(st.r[0], lmx[0], w.B0, w.B1);
+        fold_lb(st.r[1], lmx[1], w.B0, w.B1);
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
             const PairDev& P = h ? P1 : P0;
@@ -664,15 +689,17 @@ __device__ void compute_wave_pk(const PairDev& P0, const PairDev& P1, const int 
     }
     // cell (n, m) of each pair: score_max (shifted, absolute) and landing
     // column (a shorter pair's lanes stopped at its own last column)
-    if (ia == P0.n || ia + 1 == P0.n) {
-        const bool fa = ia == P0.n;
-        const uint32_t sm = psubs(fa ? st.a.SMp : st.b.SMp, k.smp), e = fa ? st.a.E : st.b.E;
-        pres0->end_SM = lo16(sm ^ kBias2) + w.B0; pres0->end_E = (PLANES & 16) ? 0 : lo16(e);
-    }
-    if (ia == P1.n || ia + 1 == P1.n) {
-        const bool fa = ia == P1.n;
-        const uint32_t sm = psubs(fa ? st.a.SMp : st.b.SMp, k.smp), e = fa ? st.a.E : st.b.E;
-        pres1->end_SM = hi16(sm ^ kBias2) + w.B1; pres1->end_E = (PLANES & 16) ? 0 : hi16(e);
+    // (the lane holding row n: its row n - ia)
+#pragma unroll
+    for (int q = 0; q < R; ++q) {
+        if (ia + q == P0.n) {
+            const uint32_t sm = psubs(st.r[q].SMp, k.smp);
+            pres0->end_SM = lo16(sm ^ kBias2) + w.B0; pres0->end_E = (PLANES & 16) ? 0 : lo16(st.r[q].E);
+        }
+        if (ia + q == P1.n) {
+            const uint32_t sm = psubs(st.r[q].SMp, k.smp);
+            pres1->end_SM = hi16(sm ^ kBias2) + w.B1; pres1->end_E = (PLANES & 16) ? 0 : hi16(st.r[q].E);
+        }
     }
 }
 
@@ -814,8 +841,10 @@ __device__ void io_wave_pk(const PairDev& P0, const PairDev& P1, const int lb, c
 // descriptors: the band queue (total_bands entries (twin q, band lb)), then
 // the twin table (ntwins entries (pair a, pair b); b == a twins a pair with
 // itself, both halves writing the same bytes).
-template <int W, int PLANES>
-__global__ __launch_bounds__((W + 1) * kWave, (W + 1 + 3) / 4) void fill_pk_kernel(
+// (R = 4: at most 128 VGPRs, four waves a SIMD, whatever the band width: the
+// 16 waves a CU of 7-wave bands two a CU, run_fill's per_cu)
+template <int W, int PLANES, int R = kRowsPerLane>
+__global__ __launch_bounds__((W + 1) * kWave, R == 4 ? 4 : (W + 1 + 3) / 4) void fill_pk_kernel(
     const PairDev* __restrict__ pairs, const int npairs, const int ntwins, const int total_bands, int* band_counter,
     PairRes* pres, StripRes* sres, const Scores32 sc) {
     __shared__ Rec rings[W + 1][kRing];
@@ -853,7 +882,7 @@ __global__ __launch_bounds__((W + 1) * kWave, (W + 1 + 3) / 4) void fill_pk_kern
             if (s < P0.strips) {
                 const bool last_in_band = wave == W - 1;
                 const bool has_consumer = last_in_band ? (lb + 1 < P0.bands) : (s + 1 < P0.strips);
-                compute_wave_pk<PLANES>(P0, P1, s, lane, sc, k, rings[wave], rings[wave + 1], (lds_int*)&wcnt[wave],
+                compute_wave_pk<PLANES, R>(P0, P1, s, lane, sc, k, rings[wave], rings[wave + 1], (lds_int*)&wcnt[wave],
                                         (lds_int*)&rcnt[wave], (lds_int*)&wcnt[wave + 1], (lds_int*)&rcnt[wave + 1],
                                         (lds_int*)bases[wave], (lds_int*)bases[wave + 1], has_consumer,
                                         pres + pa, pres + pb, band_counter + 1,
@@ -869,14 +898,19 @@ __global__ __launch_bounds__((W + 1) * kWave, (W + 1 + 3) / 4) void fill_pk_kern
 }
 
 template <int W0, int... Ws>
-static hipError_t launch_pk_w(int W, int planes, const PairDev* d_pairs, int npairs, int ntwins, int total_bands,
+static hipError_t launch_pk_w(int W, int planes, int rows, const PairDev* d_pairs, int npairs, int ntwins, int total_bands,
                               int* d_counter, PairRes* d_pres, StripRes* d_sres, Scores32 sc, int grid,
                               hipStream_t st) {
     if (W == W0) {
 #define GX_PK(PL) hipLaunchKernelGGL((fill_pk_kernel<W0, PL>), dim3(grid), dim3((W0 + 1) * kWave), 0, st, d_pairs, \
                                      npairs, ntwins, total_bands, d_counter, d_pres, d_sres, sc)
-        switch (planes) {
-#ifndef GX_PK_ONLY_LOCAL   // (register-allocation experiments: the local instantiation alone compiles in seconds)
+#define GX_PK4(PL) hipLaunchKernelGGL((fill_pk_kernel<W0, PL, 4>), dim3(grid), dim3((W0 + 1) * kWave), 0, st, d_pairs, \
+                                      npairs, ntwins, total_bands, d_counter, d_pres, d_sres, sc)
+        if (rows != kRowsPerLane && !(rows == 4 && (planes == 26 || planes == 30))) return hipErrorInvalidValue;
+        switch (rows == 4 ? planes + 64 : planes) {
+#ifndef GX_PK_ONLY_LOCAL
+            case 64 + 26: GX_PK4(26); break;   // four rows a lane (256-row strips): the batch fill
+            case 64 + 30: GX_PK4(30); break;   // (register-allocation experiments: the local instantiation alone compiles in seconds)
             case 0: GX_PK(0); break;
             case 1: GX_PK(1); break;
             case 2: GX_PK(2); break;
@@ -892,9 +926,10 @@ static hipError_t launch_pk_w(int W, int planes, const PairDev* d_pairs, int npa
             default: return hipErrorInvalidValue;
         }
 #undef GX_PK
+#undef GX_PK4
         return hipGetLastError();
     }
-    if constexpr (sizeof...(Ws) > 0) return launch_pk_w<Ws...>(W, planes, d_pairs, npairs, ntwins, total_bands,
+    if constexpr (sizeof...(Ws) > 0) return launch_pk_w<Ws...>(W, planes, rows, d_pairs, npairs, ntwins, total_bands,
                                                                d_counter, d_pres, d_sres, sc, grid, st);
     return hipErrorInvalidValue;
 }
@@ -904,14 +939,15 @@ static hipError_t launch_pk_w(int W, int planes, const PairDev* d_pairs, int npa
 // (with none or twin codes: the batch launches); + 8 (with twin codes): no
 // code words (the traceback derives them from the plane codes); + 16: no
 // skeleton; + 32 (with 2 + 8 + 16): local mode, each strip's last max of each
-// pair into d_sres (finalize_kernel reduces them).
-hipError_t launch_fill_pk(int W, int planes, const PairDev* d_pairs, int npairs, int ntwins, int total_bands,
+// pair into d_sres (finalize_kernel reduces them).  rows: rows per lane, 2
+// (128-row strips) or, with planes 26 / 30, 4 (256-row strips).
+hipError_t launch_fill_pk(int W, int planes, int rows, const PairDev* d_pairs, int npairs, int ntwins, int total_bands,
                           int* d_counter, PairRes* d_pres, StripRes* d_sres, Scores32 sc, int grid, hipStream_t st) {
 #ifndef GX_PK_ONLY_LOCAL
-    return launch_pk_w<3, 4, 7, 8, 15>(W, planes, d_pairs, npairs, ntwins, total_bands, d_counter, d_pres, d_sres, sc,
+    return launch_pk_w<3, 4, 7, 8, 15>(W, planes, rows, d_pairs, npairs, ntwins, total_bands, d_counter, d_pres, d_sres, sc,
                                        grid, st);
 #else
-    return launch_pk_w<7>(W, planes, d_pairs, npairs, ntwins, total_bands, d_counter, d_pres, d_sres, sc, grid, st);
+    return launch_pk_w<7>(W, planes, rows, d_pairs, npairs, ntwins, total_bands, d_counter, d_pres, d_sres, sc, grid, st);
 #endif
 }
 

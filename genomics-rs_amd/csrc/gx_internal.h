@@ -42,6 +42,12 @@ constexpr int kGroupInts = kRowsPerLane * kWave * 4;
 // strip = [row][lane] records
 constexpr int kTwinRec = 12;
 constexpr int kTwinGroupBytes = kRowsPerLane * kWave * kTwinRec;
+// The batch fill may give a lane four rows instead of two (gx_fill_pk.hip R,
+// 256-row strips: every per-step cost of the band pipeline is then paid once
+// per four rows); a launch's rows per lane travel in PairDev.rows, and its
+// code plane keeps the same [group][row-in-lane][lane] records, R rows a group.
+constexpr int kTwinRowsMax = 4;
+constexpr int w12_group_bytes(int rows_per_lane) { return rows_per_lane * kWave * kTwinRec; }
 // Column-step layout (layout 1): 64-row strips, lane l owns row 64s + l + 1,
 // step t = column t + 1 for every lane (no skew); planes
 // plane[strip][t/4][lane][t%4] (1 KiB per wave per plane every 4 columns),
@@ -165,7 +171,8 @@ struct __attribute__((aligned(16))) PairDev {   // 16-B multiple: the pinned sta
     int lwords;                  // words per bit row, ceil(m / kLcsBits); 0 = no LCS rows
     int lcs_waves;               // sweeping waves per LCS workgroup | (workgroups << 8) | (every row << 16)
     int lcs_base;                // the pair's first LCS workgroup (blockIdx.x)
-    int lcs_pad;
+    int rows;                    // twin fill: rows per lane of the launch, 2 or 4 (strips of 64 x rows rows;
+                                 // the plane-code decoders' address rule, gx_device.h w12_rec_off); 0 elsewhere
 };
 static_assert(sizeof(PairDev) % 16 == 0, "PairDev staging keeps the PairRes that follow it 16-B aligned");
 

@@ -1103,17 +1103,20 @@ typedef __attribute__((address_space(1))) const int gcint;
 __device__ __forceinline__ size_t tb_word(const TbDev& J, int s, int q, int rho) {
     return ((size_t)s * J.t16 + q) * J.srows + rho;
 }
-// Walked blocks are 64 rows: two per 128-row strip (layout 0), one per 64-row
-// strip (layout 1).  Row-in-strip of lane `lane` of block vb, and the step at
-// which that row computes column 1 (layout 0: the anti-diagonal skew rho/2;
-// layout 1: none).
+// Walked blocks are 64 rows: two per 128-row strip (layout 0; four per 256-row
+// strip of a twin fill with four rows a lane), one per 64-row strip (layout
+// 1).  Row-in-strip of lane `lane` of block vb, and the step at which that
+// row computes column 1 (layout 0: the anti-diagonal skew rho / rows per
+// lane; layout 1: none).
+// log2 of the walked blocks per strip = of the rows per lane (srows = 64, 128 or 256)
+__device__ __forceinline__ int tb_bsh(const TbDev& J) { return J.srows >> 7; }
 __device__ __forceinline__ int tb_rho(const TbDev& J, int vb, int lane) {
-    return J.srows == kStripRows ? ((vb & 1) << 6) + lane : lane;
+    return ((vb & ((1 << tb_bsh(J)) - 1)) << 6) + lane;
 }
 __device__ __forceinline__ int tb_lot(const TbDev& J, int rho) {
-    return J.srows == kStripRows ? rho >> 1 : J.skew ? rho : 0;   // layout 3: one row per lane, skewed
+    return J.srows != kStripRows1 ? rho >> tb_bsh(J) : J.skew ? rho : 0;   // layout 3: one row per lane, skewed
 }
-__device__ __forceinline__ int tb_strip_of(const TbDev& J, int vb) { return J.srows == kStripRows ? vb >> 1 : vb; }
+__device__ __forceinline__ int tb_strip_of(const TbDev& J, int vb) { return vb >> tb_bsh(J); }
 
 // async: words q0 .. q0+kTbWin-1 of block vb (rows 64*vb .. +63), lane = row -> buf[k][lane]
 __device__ __forceinline__ void tb_prefetch(uint32_t* buf, const TbDev& J, int vb, int q0, int lane) {
@@ -1198,7 +1201,7 @@ __device__ __forceinline__ uint32_t w16_word_of(const uint4 (&w4)[4], const int 
 // Row rho's 4-step group G of strip s in the twin code plane: the four
 // steps' dwords (gx_device.h w12_load).
 __device__ __forceinline__ uint4 w16_group(const TbDev& J, int s, int G, int rho) {
-    return w12_load(J.w16 + w12_rec_off(s, J.t4, G, rho));
+    return w12_load(J.w16 + w12_rec_off(s, J.t4, G, rho, J.srows / kWave));
 }
 // Code word q of row rho of strip s, derived from the twin plane codes.
 __device__ __forceinline__ uint32_t w16_word(const TbDev& J, int s, int q, int rho) {
@@ -1217,17 +1220,19 @@ __global__ __launch_bounds__(128) void tb_w16_codes_kernel(const TbDev* __restri
     const int j_hi = ((gcint*)seg)[4 * s + 1];
     int j_lo = (s > 0 && ((gcint*)seg)[4 * (s - 1) + 3]) ? ((gcint*)seg)[4 * (s - 1) + 1] : ((gcint*)J.end_ij)[1];
     j_lo = max(j_lo, 1);
-    const int rho = threadIdx.x, lane = rho >> 1, hh = rho & 1;
+    // (launches with skeleton and twin plane codes: two rows a lane, srows = kStripRows)
+    const int R = J.srows / kWave;
+    const int rho = threadIdx.x, lane = rho / R;
+    if (rho >= J.srows) return;
     const int q_lo = (j_lo - 1 + lane) >> 4, q_hi = min((j_hi - 1 + lane) >> 4, J.t16 - 1);
-    (void)hh;
-    const uint8_t* base = J.w16 + w12_rec_off(s, J.t4, 0, rho);
+    const uint8_t* base = J.w16 + w12_rec_off(s, J.t4, 0, rho, R);
     const int sh = 16 * J.w16_half;
-    guint* const out = (guint*)(J.codes + (size_t)s * J.t16 * kStripRows + rho);
+    guint* const out = (guint*)(J.codes + (size_t)s * J.t16 * J.srows + rho);
     for (int q = q_lo; q <= q_hi; ++q) {
         uint4 w4[4];
 #pragma unroll
-        for (int g = 0; g < 4; ++g) w4[g] = w12_load(base + (size_t)(4 * q + g) * kTwinGroupBytes);
-        out[(size_t)q * kStripRows] = w16_word_of(w4, sh);
+        for (int g = 0; g < 4; ++g) w4[g] = w12_load(base + (size_t)(4 * q + g) * w12_group_bytes(R));
+        out[(size_t)q * J.srows] = w16_word_of(w4, sh);
     }
 }
 
@@ -1326,7 +1331,7 @@ __global__ __launch_bounds__(64) void tb_strip_kernel(const TbDev* __restrict__ 
     const int j0 = __builtin_amdgcn_readfirstlane(((gcint*)J.seg)[4 * ss + 1]);
     guint* const recs = (guint*)(J.recs + (size_t)ss * J.srows);
     lint* const ltbl = (lint*)(uintptr_t)lds_addr(tbl);
-    const int vb_top = J.srows == kStripRows ? 2 * ss : ss;   // the strip's top block
+    const int vb_top = ss << tb_bsh(J);   // the strip's top block
     int vb = (i0 - 1) / kTbRows;          // current block
     int R = (i0 - 1) % kTbRows;           // the path's top lane in it
     int ce = j0;                          // its entry column
@@ -1378,7 +1383,7 @@ constexpr int kSqHelp = 4;
 struct SqCtl {
     int s, vb, R, ce, q0, done, end_i, end_j;
 };
-// words q0 .. q0 + kSqWin - 1 of block vb's rows (strip vb / 2), derived by
+// words q0 .. q0 + kSqWin - 1 of block vb's rows (strip tb_strip_of(vb)), derived by
 // the kSqHelp helper waves: helper h takes words h, h + kSqHelp, ... (all its
 // loads in flight at once)
 static_assert(kSqWin % kSqHelp == 0, "helper word split");
@@ -1386,7 +1391,7 @@ __device__ __forceinline__ void tb_seq_window(const TbDev& J, const int vb, cons
                                               const int lane) {
     typedef __attribute__((address_space(3))) uint32_t lu32w;
     lu32w* const lw = (lu32w*)(uintptr_t)lds_addr(buf);
-    const int s = vb >> 1, rho = tb_rho(J, vb, lane), sh = 16 * J.w16_half;
+    const int s = tb_strip_of(J, vb), rho = tb_rho(J, vb, lane), sh = 16 * J.w16_half;
     constexpr int kPer = kSqWin / kSqHelp;
     uint4 w4[kPer][4];
 #pragma unroll
@@ -1431,14 +1436,14 @@ __global__ __launch_bounds__((1 + kSqHelp) * kWave) void tb_seq_kernel(const TbD
     long long clk0 = stamp_clk(), walk_clk = 0;   // (diagnostics: end_ij[3])
     int nblk = 0;
     __syncthreads();
-    for (int guard = 0; guard <= 2 * J.strips + 2; ++guard) {
+    for (int guard = 0; guard <= (J.strips << tb_bsh(J)) + 2; ++guard) {
         // the next block in the walk is always vb - 1 (the strip above once vb
         // is its strip's top block); its window ends at this block's entry
         const int qn = vb > 0 ? max(((ce - 1 + tb_lot(J, tb_rho(J, vb - 1, kTbRows - 1))) >> 4) - (kSqWin - 1), 0) : 0;
         if (wave > 0) {
             if (vb > 0) tb_seq_window(J, vb - 1, qn, wbuf[cb ^ 1], wave - 1, lane);
         } else {
-            const int vb_top = 2 * s;
+            const int vb_top = s << tb_bsh(J);
             guint* const recs = (guint*)(J.recs + (size_t)s * J.srows);
             int nj;
             bool run_end;
@@ -1499,11 +1504,13 @@ __global__ __launch_bounds__(64) void plane_sums_kernel(const PairDev* __restric
                                                        unsigned long long* __restrict__ out) {
     const PairDev d = pairs[blockIdx.y];
     const int lane = threadIdx.x;
-    const int SR = lay ? kStripRows1 : kStripRows;
-    const int s = blockIdx.x / (SR / kWave);            // strip (layout 0: two blocks of 64 rows per strip)
-    const int hh = lay ? 0 : (int)(blockIdx.x & 1);     // layout 0: row-in-lane of this block
+    // rows per lane: layout 0 two (a twin fill's PairDev.rows: two or four), else one
+    const int R = lay ? 1 : (mode == 3 ? twin_rows_of(d.rows) : kRowsPerLane);
+    const int SR = kWave * R;
+    const int s = blockIdx.x / R;                       // strip (layout 0: R blocks of 64 rows per strip)
+    const int hh = (int)(blockIdx.x % R);               // layout 0: row-in-lane of this block
     if (s >= d.strips || !d.pI) return;
-    const int i = lay ? s * SR + lane + 1 : s * SR + 2 * lane + hh + 1;
+    const int i = s * SR + R * lane + hh + 1;
     const int l = lay == 1 ? 0 : lane;                  // step of column 1 on this row (layouts 0 and 3: the skew)
     const bool row_ok = i <= d.n;
     unsigned long long sI = 0, sD = 0, sS = 0;
@@ -1512,13 +1519,13 @@ __global__ __launch_bounds__(64) void plane_sums_kernel(const PairDev* __restric
     const size_t row0 = (size_t)s * d.t4 * gints + (lay ? (size_t)lane * 4 : (size_t)hh * kWave * 4 + (size_t)lane * 4);
     if (mode == 3) {   // twin plane codes (gx_fill_pk.hip w16_code): this pair's half of each dword
         const int half = d.twin_half;      // the twin's two pairs share its code plane
-        const uint8_t* base = (const uint8_t*)d.pI + w12_rec_off(s, d.t4, 0, 2 * lane + hh);
+        const uint8_t* base = (const uint8_t*)d.pI + w12_rec_off(s, d.t4, 0, R * lane + hh, R);
         const bool local = floor_ == 0;
         int I = max(h + i * g, floor_) + h;             // H(i, 0) + h, as the fill seeds it
         int mp = local ? 0 : -h;                        // (its max(S, D) - I)
         for (int q = 0; q < d.t4; ++q) {
             uint4 w4 = make_uint4(0u, 0u, 0u, 0u);
-            if (row_ok) w4 = w12_load(base + (size_t)q * kTwinGroupBytes);
+            if (row_ok) w4 = w12_load(base + (size_t)q * w12_group_bytes(R));
             const uint32_t wk[4] = {w4.x, w4.y, w4.z, w4.w};
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -1643,14 +1650,14 @@ __global__ void export_d8_kernel(const uint8_t* __restrict__ pI, const uint8_t* 
 // (PairDev.twin_half), the code plane layout [strip][t/4][row-in-lane][lane][t%4]
 // dwords.  Rows row0 .. row0 + rows - 1 (each at least 1).
 __global__ void export_w16_kernel(const uint8_t* __restrict__ codes, int half, int which, int32_t* __restrict__ out,
-                                  int n, int m, int t4, int h, int g, int floor_, int gshift, int row0, int rows) {
+                                  int n, int m, int t4, int h, int g, int floor_, int gshift, int row0, int rows,
+                                  int R) {
     const int r = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     const int i = r + row0;
     if (r >= rows || i < 1 || i > n) return;
-    const int s = (i - 1) / kStripRows, rho = (i - 1) % kStripRows;
-    const int l = rho >> 1, hh = rho & 1;
-    (void)hh;
-    const uint8_t* base = codes + w12_rec_off(s, t4, 0, rho);
+    const int s = (i - 1) / (kWave * R), rho = (i - 1) % (kWave * R);   // R: the fill's rows per lane
+    const int l = rho / R;
+    const uint8_t* base = codes + w12_rec_off(s, t4, 0, rho, R);
     const bool local = floor_ == 0;
     (void)gshift;
     int I = max(h + i * g, floor_) + h;   // H(i, 0) + h, as the fill seeds it
@@ -1659,7 +1666,7 @@ __global__ void export_w16_kernel(const uint8_t* __restrict__ codes, int half, i
     uint4 rec = make_uint4(0u, 0u, 0u, 0u);
     for (int j = 1; j <= m; ++j) {
         const int t = j - 1 + l;
-        if (j == 1 || (t & 3) == 0) rec = w12_load(base + (size_t)(t >> 2) * kTwinGroupBytes);
+        if (j == 1 || (t & 3) == 0) rec = w12_load(base + (size_t)(t >> 2) * w12_group_bytes(R));
         const uint32_t wd = (t & 3) == 0 ? rec.x : (t & 3) == 1 ? rec.y : (t & 3) == 2 ? rec.z : rec.w;
         int xS, xD;
         w16_decode((wd >> (16 * half)) & 0xFFFFu, xS, xD);
@@ -1770,10 +1777,10 @@ hipError_t launch_export_d8(const uint8_t* pI, const uint8_t* px, int32_t* out, 
 }
 
 hipError_t launch_export_w16(const uint8_t* codes, int half, int which, int32_t* out, int n, int m, int t4, int h,
-                             int g, int floor_, int gshift, int row0, int rows, hipStream_t st) {
+                             int g, int floor_, int gshift, int row0, int rows, int rows_per_lane, hipStream_t st) {
     if (n == 0 || m == 0 || rows <= 0) return hipSuccess;
     hipLaunchKernelGGL(export_w16_kernel, dim3((unsigned)((rows + 63) / 64)), dim3(64), 0, st, codes, half, which, out,
-                       n, m, t4, h, g, floor_, gshift, row0, rows);
+                       n, m, t4, h, g, floor_, gshift, row0, rows, rows_per_lane == 4 ? 4 : kRowsPerLane);
     return hipGetLastError();
 }
 
@@ -1807,9 +1814,9 @@ __global__ __launch_bounds__(64) void local_col_kernel(const PairDev* __restrict
     const int lane = threadIdx.x;
     const int i = __builtin_amdgcn_readfirstlane(r->lmax_i), target = __builtin_amdgcn_readfirstlane(r->lmax_val);
     if (i < 1 || i > d.n || d.m < 1 || !d.pI) return;
-    const int s = (i - 1) / kStripRows, rr = (i - 1) % kStripRows, l = rr >> 1, hh = rr & 1;
-    (void)hh;
-    const uint8_t* base = (const uint8_t*)d.pI + w12_rec_off(s, d.t4, 0, rr);
+    // (the local twin fill keeps two rows a lane)
+    const int s = (i - 1) / kStripRows, rr = (i - 1) % kStripRows, l = rr / kRowsPerLane;
+    const uint8_t* base = (const uint8_t*)d.pI + w12_rec_off(s, d.t4, 0, rr, kRowsPerLane);
     const int sh = 16 * d.twin_half;
     const int C = (d.m + kWave - 1) / kWave, j0 = lane * C + 1, j1 = min(d.m, j0 + C - 1);
     auto code_at = [&](int j, int& xS, int& xD) {
@@ -1856,11 +1863,12 @@ hipError_t launch_local_col(const PairDev* d_pairs, int npairs, PairRes* d_pres,
 }
 
 hipError_t launch_plane_sums(const PairDev* d_pairs, int npairs, int max_strips, int lay, int mode, int h, int g,
-                             int floor_, int gshift, unsigned long long* out, hipStream_t st) {
+                             int floor_, int gshift, unsigned long long* out, int rows_per_lane, hipStream_t st) {
     if (npairs <= 0 || max_strips <= 0) return hipSuccess;
     hipError_t e = hipMemsetAsync(out, 0, (size_t)npairs * 3 * sizeof(unsigned long long), st);
     if (e != hipSuccess) return e;
-    const int blocks = max_strips * (lay ? 1 : kStripRows / kWave);
+    // one block per 64 rows: rows_per_lane of them a strip (layout 0: two, a twin fill's four)
+    const int blocks = max_strips * (lay ? 1 : rows_per_lane == 4 ? 4 : kRowsPerLane);
     hipLaunchKernelGGL(plane_sums_kernel, dim3((unsigned)blocks, (unsigned)npairs), dim3(64), 0, st, d_pairs, lay,
                        mode, h, g, floor_, gshift, out);
     return hipGetLastError();

@@ -88,7 +88,7 @@ EXPORTED = ["gx_last_error", "gx_version", "gx_context_create", "gx_context_dest
             "gx_stage_pairs",
             "gx_run_staged", "gx_run_staged_steps", "gx_staged_plane_sums", "gx_staged_steps",
             "gx_staged_pass_results", "gx_fill_info", "gx_batch_chunks", "gx_fill_twin", "gx_fill_groups", "gx_fill_plane_bits", "gx_plane_bytes_per_cell", "gx_twin_admission",
-            "gx_twin_admission_mode", "gx_plan_layout", "gx_staged_table",
+            "gx_twin_admission_mode", "gx_twin_admission_rows", "gx_fill_rows", "gx_plan_layout", "gx_staged_table",
             "gx_fasta_load",
             "gx_config_load", "gx_format_alignment", "gx_format_table",
             "gx_common_substring_host", "gx_common_substring", "gx_compare_pair", "gx_compare_matrix",
@@ -151,6 +151,10 @@ def lib():
                                     ctypes.POINTER(ctypes.c_int64)]
     L.gx_twin_admission_mode.argtypes = [ctypes.POINTER(CScores), ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                          ctypes.POINTER(ctypes.c_int64)]
+    if hasattr(L, "gx_twin_admission_rows"):   # (absent from builds before the 256-row strips, run for A/B timing)
+        L.gx_twin_admission_rows.argtypes = [ctypes.POINTER(CScores), ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                             ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
+        L.gx_fill_rows.argtypes = [vp]
     L.gx_staged_table.argtypes = [vp, sz, ctypes.POINTER(vp)]
     L.gx_plan_layout.argtypes = [ctypes.POINTER(CScores), ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
                                  ctypes.POINTER(ctypes.c_int64), sz, ctypes.c_int, ctypes.c_int]
@@ -355,13 +359,19 @@ def plan_layout(scores: "Scores", is_local: bool, shapes: Seq[Tuple[int, int]], 
                                 int(grid_cap))
 
 
-def twin_admission(scores: "Scores", band_waves: int, col_gap: int = 0, is_local: bool = False) -> Tuple[bool, int]:
+def twin_admission(scores: "Scores", band_waves: int, col_gap: int = 0, is_local: bool = False,
+                   rows_per_lane: int = 2) -> Tuple[bool, int]:
     """The twin fill's int16 admission rule (gx_twin_admission_mode): (admitted,
     bound), bound = the largest |value - base| a band of `band_waves` strips
-    can reach when a twin's pairs differ by up to col_gap columns."""
+    can reach when a twin's pairs differ by up to col_gap columns.
+    rows_per_lane = 4: the rule of the 256-row strips (gx_twin_admission_rows)."""
     b = ctypes.c_int64(0)
-    r = lib().gx_twin_admission_mode(ctypes.byref(scores.c()), int(bool(is_local)), int(band_waves), int(col_gap),
-                                     ctypes.byref(b))
+    if rows_per_lane != 2:
+        r = lib().gx_twin_admission_rows(ctypes.byref(scores.c()), int(bool(is_local)), int(band_waves),
+                                         int(col_gap), int(rows_per_lane), ctypes.byref(b))
+    else:
+        r = lib().gx_twin_admission_mode(ctypes.byref(scores.c()), int(bool(is_local)), int(band_waves), int(col_gap),
+                                         ctypes.byref(b))
     if r < 0:
         raise GxError(3, "invalid scores")
     return bool(r), int(b.value)
@@ -392,7 +402,8 @@ class Context:
         return {"layout": v[0].value, "band_waves": v[1].value,
                 "plane_bytes_per_cell": bits // 8 if bits % 8 == 0 else bits / 8,   # (twin codes: 1.5)
                 "chunks": lib().gx_batch_chunks(self.ptr), "twin": lib().gx_fill_twin(self.ptr),
-                "groups": lib().gx_fill_groups(self.ptr)}
+                "groups": lib().gx_fill_groups(self.ptr),
+                "twin_rows": lib().gx_fill_rows(self.ptr) if hasattr(lib(), "gx_fill_rows") else 2}
 
     def __del__(self):
         try:

@@ -260,6 +260,10 @@ int gx_batch_chunks(const gx_context* ctx);
  * Measurement only (GX_TWIN=0 disables it, GX_TWIN=1 forces it where the
  * range bound admits it; by default deep band queues take it). */
 int gx_fill_twin(const gx_context* ctx);
+/* Rows per lane of the last fill launch when it was the twin fill: 2 (128-row
+ * strips) or 4 (256-row strips; GX_TWIN_ROWS=2|4 forces either where it can
+ * be launched), 0 for every other fill, -1 without a context.  Measurement only. */
+int gx_fill_rows(const gx_context* ctx);
 
 /* Fill launches per pass of the last staged / batch call: 2 when the pairs
  * ran as two groups whose walks overlap the next pass's fills (a batch of
@@ -286,6 +290,13 @@ int gx_twin_admission(const gx_scores* scores, int band_waves, int64_t col_gap, 
  * max(|h + g|, U) of the unshifted values and the floor's constants
  * (DESIGN.md 6.7).  Same returns as gx_twin_admission. */
 int gx_twin_admission_mode(const gx_scores* scores, int is_local, int band_waves, int64_t col_gap, int64_t* bound);
+/* The same rule for a fill with rows_per_lane rows a lane: 2 (128-row strips,
+ * the value gx_twin_admission_mode gives) or 4 (the global batch fill's 256-row
+ * strips: a strip then spans 320 instead of 192 neighbour steps, DESIGN.md
+ * 6.5).  Local fills keep two rows a lane: 0 at four.  -1 on invalid scores or
+ * any other rows_per_lane. */
+int gx_twin_admission_rows(const gx_scores* scores, int is_local, int band_waves, int64_t col_gap,
+                           int rows_per_lane, int64_t* bound);
 /* The fill layout a launch of these pair shapes would take (host rule only,
  * no device): 0 = anti-diagonal 128-row strips (batches), 1 = the column
  * step, 3 = skewed 64-row strips (the latency layouts);
