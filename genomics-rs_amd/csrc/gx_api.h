@@ -303,6 +303,7 @@ struct gx_context {
     int last_chunks = 1;                             // chunks of the last staged / batch call
     int last_twin = 0;                               // the last fill was the twin (packed 16-bit) fill
     int last_rows = 0;                               // ... its rows per lane (2 or 4; 0: not the twin fill)
+    int last_tbl = 0;                                // ... used the small-alphabet score tables (gx_fill_score_table)
     int last_groups = 1;                             // fill launches per pass of the last staged / batch call
     // GX_STAGED_PLANE_SUMS: plane checksums of every pass of a staged run
     DevBuf sums_dev;
@@ -506,6 +507,22 @@ std::vector<std::pair<int, int>> twin_table(const std::vector<PairHost>& ph, lon
 int twin_width(const std::vector<PairHost>& ph, const std::vector<std::pair<int, int>>& tw, const Scores32& sc,
                int is_local, bool track, bool lcs, int lay, bool planes, bool d8, int W_want,
                bool long_ok = false, int rows = kRowsPerLane);
+// GX_TWIN_ROWS, GX_BAND_WAVES and GX_FILL_GRID as read from the environment (nullptr: unset)
+struct TwinEnv {
+    const char* rows;
+    const char* band_waves;
+    const char* fill_grid;
+    static TwinEnv read();
+};
+// A launch's twin decision: its twins, band width (0: not the twin fill), rows per lane, twin plane codes
+struct TwinPlan {
+    std::vector<std::pair<int, int>> tw;
+    int W = 0;
+    int rows = kRowsPerLane;
+    bool w16 = false;
+};
+TwinPlan twin_plan(const std::vector<PairHost>& ph, const Scores32& sc, int is_local, bool planes, bool track,
+                   bool lcs, bool table, int lay, bool d8, int grid_cap, const TwinEnv& env);
 double pair_device_bytes(size_t n, size_t m, double plane_bpc);   // one pair's device bytes in a batch
 double chunk_budget(gx_context* ctx);                             // device bytes one chunk may use
 std::vector<std::pair<size_t, size_t>> plan_chunks(gx_context* ctx, const std::vector<PairHost>& ph,

@@ -83,62 +83,19 @@ int run_fill(gx_context* ctx, const std::vector<std::pair<const uint8_t*, const 
     job.lcs_rows = lay == 3 && track;
     const bool d8 = planes && lay == 0 && !track && d8_planes_ok(sc, is_local);
     job.d8 = d8;
-    // twin fill: half as many band jobs (each carries two pairs); the band
-    // width follows the usual rule on the twins' strips (GX_BAND_WAVES forces it)
-    int Wt = 0;
-    int wt_want = 15;
-    if (const char* e = getenv("GX_BAND_WAVES")) wt_want = atoi(e);
-    else wt_want = fill_band_waves(false, total_strips / 2, fill_grid_cap(ctx->device), lay, min_strips);
-    const std::vector<std::pair<int, int>> tw = twin_table(
-        ph, twin_gap_cap(sc, wt_want >= 15 ? 15 : wt_want >= 8 ? 8 : wt_want >= 7 ? 7 : wt_want >= 4 ? 4 : 3,
-                         is_local != 0));
-    {
-        const bool long_ok = planes && !job.table && w16_ok(sc);   // (the noskel rule below)
-        Wt = twin_width(ph, tw, sc, is_local, track, lcs, lay, planes, d8, wt_want, long_ok);
-        // auto: the twin fill once its own bands fill the grid (a twin band
-        // is slower per step than a scalar one, so fewer bands than CUs
-        // leave it latency-bound).  30k pairs, fill ms scalar / twin (codes,
-        // tables): 4 pairs (158 twin bands) 7.2 / 8.8, 6 (237) 9.4 / 8.9,
-        // 8 9.96 / 8.9, 16 14.1 / 12.9, 24 19.2 / 17.4, all-vs-all and 80
-        // pairs far apart.  GX_TWIN=1 forces it.
-        const char* e = getenv("GX_TWIN");
-        if (Wt && !(e && !strcmp(e, "1"))) {
-            long long twin_bands = 0;
-            for (const auto& t : tw)
-                twin_bands += ceil_div(ceil_div((int)std::max(ph[t.first].n, ph[t.second].n), SR), Wt);
-            if (10 * twin_bands < 9LL * fill_grid_cap(ctx->device)) Wt = 0;
-            // a pair twinned with itself does a twin band's work for one pair:
-            // batches of mostly unmatched shapes stay on the scalar fill
-            size_t selfs = 0;
-            for (const auto& t : tw) selfs += t.first == t.second;
-            if (4 * selfs > tw.size() + 3) Wt = 0;
-        }
-        // 7-wave bands, two workgroups per CU (16 waves: the twin fill's 128
-        // VGPRs allow four a SIMD; 8-wave bands fit one), for global batches
-        // of pairs of >= 32 strips (4,096 rows) with >= 1.25 such bands per
-        // workgroup of that grid: the CU then holds two independent band
-        // pipelines.  80 x 30k (each overlapped group 680 bands on 512
-        // workgroups) fill 26.8 -> 24.6 ms a pass (2,616 -> 2,852 GCUPS),
-        // 1024 x 16k (1,216) 99.5 -> 95.0, 1024 x 4k 7.59 -> 6.78 ms a pass and
-        // 8k 26.7 -> 23.9 (with the walk on the fill's stream: beside the
-        // fill, 1,024 walks found no room on the CUs, 4k once 72 ms a pass;
-        // batch_core_steps); slower with fewer bands (all-vs-all with planes,
-        // 374-408: 16.7 -> 18.5 ms), for 2k pairs (2.25 -> 2.38 ms) and for
-        // the local twin (64 related 30k pairs 1,852 -> 1,359 GCUPS)
-        // (profiles/r05_w7_sweep.txt)
-        if (Wt == 8 && !is_local && long_ok && !getenv("GX_BAND_WAVES") && min_strips >= 32) {
-            long long b7 = 0;
-            for (const auto& t : tw) b7 += ceil_div(ceil_div((int)std::max(ph[t.first].n, ph[t.second].n), SR), 7);
-            if (4 * b7 >= 5LL * 2 * fill_grid_cap(ctx->device)) Wt = 7;
-        }
-    }
+    // the twin fill (half as many band jobs, each carrying two pairs): whether
+    // this launch takes it, its twins, band width and rows per lane (gx_api_plan.cpp twin_plan)
+    const TwinPlan tp = twin_plan(ph, sc, is_local, planes, track, lcs, job.table, lay, d8,
+                                  fill_grid_cap(ctx->device), TwinEnv::read());
+    const std::vector<std::pair<int, int>>& tw = tp.tw;
+    const int Wt = tp.W;
     const bool twin = Wt > 0;
     job.twin = twin;
     if (twin && is_local) {   // the local twin's scores carry + K so that its score tables hold bytes >= 0
         const int K = std::max(0, -std::min(sc.sm, sc.smm));
         scl.koff = K; scl.sm = sc.sm + K; scl.smm = sc.smm + K;
     }
-    const bool w16 = twin && planes && !job.table && w16_ok(sc);
+    const bool w16 = tp.w16;
     job.w16 = w16;
     // with twin plane codes the fill stores no code words (0.25 B/cell less):
     // the traceback rebuilds the words of the path's strips from the planes
@@ -148,39 +105,7 @@ int run_fill(gx_context* ctx, const std::vector<std::pair<const uint8_t*, const 
     // planes (tables, GX_PLANES_W16=0) keep both.
     job.nocodes = w16;
     job.noskel = job.nocodes;
-    // Rows per lane.  Four (256-row strips, gx_fill_pk.hip R = 4) halve how
-    // often the band pipeline's per-step work runs per cell: the ring reads
-    // and pushes, the DPP hand-down, the counters and polls, the I/O wave's
-    // chunks and the band hand-off rows.  Only the global fill with twin
-    // codes and neither code words nor skeleton has that instantiation, and
-    // only launches whose admission bound holds at the taller strips
-    // (twin_bound's span, 320 instead of 192 neighbour steps a strip) take
-    // it; the band width is picked again on the 256-row strips.
-    // GX_TWIN_ROWS=2|4 forces the choice where it is launchable.  Unasked,
-    // four rows are taken only by the default launch: the rule was measured
-    // at the device's own grid and its own band width, so a launch whose band
-    // width or grid is given (GX_BAND_WAVES, GX_FILL_GRID) keeps two rows and
-    // the width it asked for (15-strip bands are not admitted at four rows).
-    int rows = kRowsPerLane;
-    if (twin && w16 && !is_local && !track && lay == 0) {
-        const int SR4 = kWave * kTwinRowsMax;
-        int strips4 = 0, min4 = INT_MAX;
-        for (const PairHost& h : ph) {
-            strips4 += ceil_div((int)h.n, SR4);
-            min4 = std::min(min4, ceil_div((int)h.n, SR4));
-        }
-        const char* e = getenv("GX_TWIN_ROWS");
-        const int force = e ? atoi(e) : 0;
-        const bool plain = !getenv("GX_BAND_WAVES") && !getenv("GX_FILL_GRID");
-        const bool want4 = force == 4 ||
-                           (force != 2 && plain && twin_rows4_auto(min4, strips4 / 2, fill_grid_cap(ctx->device)));
-        if (want4) {
-            const char* bw = getenv("GX_BAND_WAVES");
-            const int want = bw ? atoi(bw) : twin_rows4_band_waves(strips4 / 2, fill_grid_cap(ctx->device), min4);
-            const int W4 = twin_width(ph, tw, sc, is_local, track, lcs, lay, planes, d8, want, true, kTwinRowsMax);
-            if (W4 > 0) { rows = kTwinRowsMax; Wt = W4; }   // (not admitted at any width: two rows a lane)
-        }
-    }
+    const int rows = tp.rows;   // per lane: 4 = 256-row strips (gx_fill_pk.hip R), twin_plan's rule
     job.rows = rows;
     const int SRf = twin ? kWave * rows : SR;   // rows per strip of the launch
     // small-alphabet twins: the match test through score tables (cell_pk; the
@@ -190,6 +115,7 @@ int run_fill(gx_context* ctx, const std::vector<std::pair<const uint8_t*, const 
                           scl.smm <= 255;
     ctx->last_twin = twin ? 1 : 0;
     ctx->last_rows = twin ? rows : 0;
+    ctx->last_tbl = (twin ? twin_tbl : tbl) ? 1 : 0;
     const int Wf = twin ? Wt : W;   // band width of the launch
     const size_t plane_esz = d8 ? 1 : sizeof(int32_t);
     job.W = Wf;

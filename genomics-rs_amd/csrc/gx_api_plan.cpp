@@ -1,8 +1,8 @@
 // gx_api_plan.cpp -- launch planning on the host: the exact-int32 range
 // guard and analytic boundary cells (algo.rs:193-220), the fill layout /
 // band width / plane format choice, twin pairing, batch chunks, and the
-// planning queries of the C ABI (gx_plan_layout, gx_twin_admission*,
-// gx_plane_bytes_per_cell).
+// planning queries of the C ABI (gx_plan_layout, gx_plan_twin_rows,
+// gx_twin_admission*, gx_plane_bytes_per_cell).
 #include "gx_api.h"
 
 // ---------------------------------------------------------------------------
@@ -434,6 +434,107 @@ int twin_rows4_band_waves(int twin_strips4, int grid_cap, int min_strips4) {
     return std::min(8, fill_band_waves(false, twin_strips4, grid_cap, 0, min_strips4));
 }
 
+TwinEnv TwinEnv::read() { return TwinEnv{getenv("GX_TWIN_ROWS"), getenv("GX_BAND_WAVES"), getenv("GX_FILL_GRID")}; }
+
+// Whether a launch is the twin fill, its twins, band width and rows per lane
+// (run_fill and gx_plan_twin_rows).  track / lcs as run_fill holds them (lcs
+// only with planes, track including lcs); table: an alignment table's fill
+// (FillJob.table); grid_cap: fill_grid_cap of the device.
+TwinPlan twin_plan(const std::vector<PairHost>& ph, const Scores32& sc, int is_local, bool planes, bool track,
+                   bool lcs, bool table, int lay, bool d8, int grid_cap, const TwinEnv& env) {
+    TwinPlan tp;
+    const int SR = strip_rows(lay);
+    int total_strips = 0, min_strips = INT_MAX;
+    for (const PairHost& h : ph) {
+        total_strips += ceil_div((int)h.n, SR);
+        min_strips = std::min(min_strips, ceil_div((int)h.n, SR));
+    }
+    // twin fill: half as many band jobs (each carries two pairs); the band
+    // width follows the usual rule on the twins' strips (GX_BAND_WAVES forces it)
+    int Wt = 0;
+    int wt_want = 15;
+    if (env.band_waves) wt_want = atoi(env.band_waves);
+    else wt_want = fill_band_waves(false, total_strips / 2, grid_cap, lay, min_strips);
+    tp.tw = twin_table(
+        ph, twin_gap_cap(sc, wt_want >= 15 ? 15 : wt_want >= 8 ? 8 : wt_want >= 7 ? 7 : wt_want >= 4 ? 4 : 3,
+                         is_local != 0));
+    const std::vector<std::pair<int, int>>& tw = tp.tw;
+    const bool long_ok = planes && !table && w16_ok(sc);   // (the noskel rule of run_fill)
+    {
+        Wt = twin_width(ph, tw, sc, is_local, track, lcs, lay, planes, d8, wt_want, long_ok);
+        // auto: the twin fill once its own bands fill the grid (a twin band
+        // is slower per step than a scalar one, so fewer bands than CUs
+        // leave it latency-bound).  30k pairs, fill ms scalar / twin (codes,
+        // tables): 4 pairs (158 twin bands) 7.2 / 8.8, 6 (237) 9.4 / 8.9,
+        // 8 9.96 / 8.9, 16 14.1 / 12.9, 24 19.2 / 17.4, all-vs-all and 80
+        // pairs far apart.  GX_TWIN=1 forces it.
+        const char* e = getenv("GX_TWIN");
+        if (Wt && !(e && !strcmp(e, "1"))) {
+            long long twin_bands = 0;
+            for (const auto& t : tw)
+                twin_bands += ceil_div(ceil_div((int)std::max(ph[t.first].n, ph[t.second].n), SR), Wt);
+            if (10 * twin_bands < 9LL * grid_cap) Wt = 0;
+            // a pair twinned with itself does a twin band's work for one pair:
+            // batches of mostly unmatched shapes stay on the scalar fill
+            size_t selfs = 0;
+            for (const auto& t : tw) selfs += t.first == t.second;
+            if (4 * selfs > tw.size() + 3) Wt = 0;
+        }
+        // 7-wave bands, two workgroups per CU (16 waves: the twin fill's 128
+        // VGPRs allow four a SIMD; 8-wave bands fit one), for global batches
+        // of pairs of >= 32 strips (4,096 rows) with >= 1.25 such bands per
+        // workgroup of that grid: the CU then holds two independent band
+        // pipelines.  80 x 30k (each overlapped group 680 bands on 512
+        // workgroups) fill 26.8 -> 24.6 ms a pass (2,616 -> 2,852 GCUPS),
+        // 1024 x 16k (1,216) 99.5 -> 95.0, 1024 x 4k 7.59 -> 6.78 ms a pass and
+        // 8k 26.7 -> 23.9 (with the walk on the fill's stream: beside the
+        // fill, 1,024 walks found no room on the CUs, 4k once 72 ms a pass;
+        // batch_core_steps); slower with fewer bands (all-vs-all with planes,
+        // 374-408: 16.7 -> 18.5 ms), for 2k pairs (2.25 -> 2.38 ms) and for
+        // the local twin (64 related 30k pairs 1,852 -> 1,359 GCUPS)
+        // (profiles/r05_w7_sweep.txt)
+        if (Wt == 8 && !is_local && long_ok && !env.band_waves && min_strips >= 32) {
+            long long b7 = 0;
+            for (const auto& t : tw) b7 += ceil_div(ceil_div((int)std::max(ph[t.first].n, ph[t.second].n), SR), 7);
+            if (4 * b7 >= 5LL * 2 * grid_cap) Wt = 7;
+        }
+    }
+    const bool twin = Wt > 0;
+    tp.w16 = twin && long_ok;
+    // Rows per lane.  Four (256-row strips, gx_fill_pk.hip R = 4) halve how
+    // often the band pipeline's per-step work runs per cell: the ring reads
+    // and pushes, the DPP hand-down, the counters and polls, the I/O wave's
+    // chunks and the band hand-off rows.  Only the global fill with twin
+    // codes and neither code words nor skeleton has that instantiation, and
+    // only launches whose admission bound holds at the taller strips
+    // (twin_bound's span, 320 instead of 192 neighbour steps a strip) take
+    // it; the band width is picked again on the 256-row strips.
+    // GX_TWIN_ROWS=2|4 forces the choice where it is launchable.  Unasked,
+    // four rows are taken only by the default launch: the rule was measured
+    // at the device's own grid and its own band width, so a launch whose band
+    // width or grid is given (GX_BAND_WAVES, GX_FILL_GRID) keeps two rows and
+    // the width it asked for (15-strip bands are not admitted at four rows
+    // at the default scores).
+    if (twin && tp.w16 && !is_local && !track && lay == 0) {
+        const int SR4 = kWave * kTwinRowsMax;
+        int strips4 = 0, min4 = INT_MAX;
+        for (const PairHost& h : ph) {
+            strips4 += ceil_div((int)h.n, SR4);
+            min4 = std::min(min4, ceil_div((int)h.n, SR4));
+        }
+        const int force = env.rows ? atoi(env.rows) : 0;
+        const bool plain = !env.band_waves && !env.fill_grid;
+        const bool want4 = force == 4 || (force != 2 && plain && twin_rows4_auto(min4, strips4 / 2, grid_cap));
+        if (want4) {
+            const int want = env.band_waves ? atoi(env.band_waves) : twin_rows4_band_waves(strips4 / 2, grid_cap, min4);
+            const int W4 = twin_width(ph, tw, sc, is_local, track, lcs, lay, planes, d8, want, true, kTwinRowsMax);
+            if (W4 > 0) { tp.rows = kTwinRowsMax; Wt = W4; }   // (not admitted at any width: two rows a lane)
+        }
+    }
+    tp.W = Wt;
+    return tp;
+}
+
 // ---------------------------------------------------------------------------
 // chunked batches: a batch whose device footprint exceeds the free HBM runs
 // as contiguous chunks of pairs through the same (reused) device buffers
@@ -573,6 +674,30 @@ extern "C" int gx_plan_layout(const gx_scores* scores, int is_local, const int64
     std::vector<PairHost> ph(npairs);
     for (size_t p = 0; p < npairs; ++p) ph[p] = PairHost{nullptr, nullptr, (size_t)n[p], (size_t)m[p]};
     return fill_layout(ph, sc, grid_cap > 0 ? grid_cap : 256, track != 0, false);
+}
+
+extern "C" int gx_plan_twin_rows(const gx_scores* scores, const int64_t* n, const int64_t* m, size_t npairs,
+                                 int grid_cap, int* band_waves) {
+    if (!scores || !n || !m || npairs == 0) return -1;
+    int64_t nmax = 0, mmax = 0;
+    for (size_t p = 0; p < npairs; ++p) {
+        if (n[p] < 1 || m[p] < 1) return -1;   // (a staged launch holds the pairs with an interior only)
+        nmax = std::max(nmax, n[p]); mmax = std::max(mmax, m[p]);
+    }
+    HostScores hs;
+    Scores32 sc;
+    if (check_scores(scores, (size_t)nmax, (size_t)mmax, &hs, &sc, 0, nullptr) != GX_OK) return -1;
+    std::vector<PairHost> ph(npairs);
+    for (size_t p = 0; p < npairs; ++p) ph[p] = PairHost{nullptr, nullptr, (size_t)n[p], (size_t)m[p]};
+    const TwinEnv env = TwinEnv::read();
+    int cap = grid_cap > 0 ? grid_cap : 256;
+    if (env.fill_grid && atoi(env.fill_grid) > 0) cap = atoi(env.fill_grid);   // (as fill_grid_cap)
+    // run_fill's inputs for a global staged batch with planes: untracked, no table
+    const int lay = fill_layout(ph, sc, cap, false, false);
+    const bool d8 = lay == 0 && d8_planes_ok(sc, 0);
+    const TwinPlan tp = twin_plan(ph, sc, 0, true, false, false, false, lay, d8, cap, env);
+    if (band_waves) *band_waves = tp.W;
+    return tp.rows;
 }
 
 extern "C" int gx_plane_bytes_per_cell(const gx_scores* scores, int is_local) {

@@ -345,6 +345,7 @@ extern "C" int gx_staged_steps(const gx_context* ctx, size_t pair, gx_step* step
 extern "C" int gx_batch_chunks(const gx_context* ctx) { return ctx ? ctx->last_chunks : -1; }
 extern "C" int gx_fill_twin(const gx_context* ctx) { return ctx ? ctx->last_twin : -1; }
 extern "C" int gx_fill_rows(const gx_context* ctx) { return ctx ? ctx->last_rows : -1; }
+extern "C" int gx_fill_score_table(const gx_context* ctx) { return ctx ? ctx->last_tbl : -1; }
 extern "C" int gx_fill_groups(const gx_context* ctx) { return ctx ? ctx->last_groups : -1; }
 extern "C" int gx_fill_plane_bits(const gx_context* ctx) { return ctx ? ctx->last_pbits : -1; }
 

@@ -88,7 +88,8 @@ EXPORTED = ["gx_last_error", "gx_version", "gx_context_create", "gx_context_dest
             "gx_stage_pairs",
             "gx_run_staged", "gx_run_staged_steps", "gx_staged_plane_sums", "gx_staged_steps",
             "gx_staged_pass_results", "gx_fill_info", "gx_batch_chunks", "gx_fill_twin", "gx_fill_groups", "gx_fill_plane_bits", "gx_plane_bytes_per_cell", "gx_twin_admission",
-            "gx_twin_admission_mode", "gx_twin_admission_rows", "gx_fill_rows", "gx_plan_layout", "gx_staged_table",
+            "gx_twin_admission_mode", "gx_twin_admission_rows", "gx_fill_rows", "gx_fill_score_table", "gx_plan_layout",
+            "gx_plan_twin_rows", "gx_staged_table",
             "gx_fasta_load",
             "gx_config_load", "gx_format_alignment", "gx_format_table",
             "gx_common_substring_host", "gx_common_substring", "gx_compare_pair", "gx_compare_matrix",
@@ -155,6 +156,11 @@ def lib():
         L.gx_twin_admission_rows.argtypes = [ctypes.POINTER(CScores), ctypes.c_int, ctypes.c_int, ctypes.c_int64,
                                              ctypes.c_int, ctypes.POINTER(ctypes.c_int64)]
         L.gx_fill_rows.argtypes = [vp]
+    if hasattr(L, "gx_fill_score_table"):   # (absent from earlier builds run for A/B timing)
+        L.gx_fill_score_table.argtypes = [vp]
+        L.gx_plan_twin_rows.argtypes = [ctypes.POINTER(CScores), ctypes.POINTER(ctypes.c_int64),
+                                        ctypes.POINTER(ctypes.c_int64), sz, ctypes.c_int,
+                                        ctypes.POINTER(ctypes.c_int)]
     L.gx_staged_table.argtypes = [vp, sz, ctypes.POINTER(vp)]
     L.gx_plan_layout.argtypes = [ctypes.POINTER(CScores), ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
                                  ctypes.POINTER(ctypes.c_int64), sz, ctypes.c_int, ctypes.c_int]
@@ -359,6 +365,20 @@ def plan_layout(scores: "Scores", is_local: bool, shapes: Seq[Tuple[int, int]], 
                                 int(grid_cap))
 
 
+def plan_twin_rows(scores: "Scores", shapes: Seq[Tuple[int, int]], grid_cap: int = 0) -> Tuple[int, int]:
+    """(rows per lane, band width) a global staged launch of these (n, m) pair
+    shapes with planes would take (gx_plan_twin_rows; host rule only, no
+    device): rows 4 or 2, band width 0 when it would not be the twin fill."""
+    k = len(shapes)
+    n = (ctypes.c_int64 * max(k, 1))(*[a for a, _ in shapes])
+    m = (ctypes.c_int64 * max(k, 1))(*[b for _, b in shapes])
+    w = ctypes.c_int(0)
+    r = lib().gx_plan_twin_rows(ctypes.byref(scores.c()), n, m, k, int(grid_cap), ctypes.byref(w))
+    if r < 0:
+        raise GxError(3, "invalid scores or shapes")
+    return r, int(w.value)
+
+
 def twin_admission(scores: "Scores", band_waves: int, col_gap: int = 0, is_local: bool = False,
                    rows_per_lane: int = 2) -> Tuple[bool, int]:
     """The twin fill's int16 admission rule (gx_twin_admission_mode): (admitted,
@@ -403,7 +423,8 @@ class Context:
                 "plane_bytes_per_cell": bits // 8 if bits % 8 == 0 else bits / 8,   # (twin codes: 1.5)
                 "chunks": lib().gx_batch_chunks(self.ptr), "twin": lib().gx_fill_twin(self.ptr),
                 "groups": lib().gx_fill_groups(self.ptr),
-                "twin_rows": lib().gx_fill_rows(self.ptr) if hasattr(lib(), "gx_fill_rows") else 2}
+                "twin_rows": lib().gx_fill_rows(self.ptr) if hasattr(lib(), "gx_fill_rows") else 2,
+                "score_table": lib().gx_fill_score_table(self.ptr) if hasattr(lib(), "gx_fill_score_table") else -1}
 
     def __del__(self):
         try:

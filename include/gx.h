@@ -264,6 +264,11 @@ int gx_fill_twin(const gx_context* ctx);
  * strips) or 4 (256-row strips; GX_TWIN_ROWS=2|4 forces either where it can
  * be launched), 0 for every other fill, -1 without a context.  Measurement only. */
 int gx_fill_rows(const gx_context* ctx);
+/* 1 when the last fill launch on ctx took its match / mismatch scores from the
+ * small-alphabet score tables (at most 4 distinct symbols and scores that fit
+ * the tables' bytes; GX_NO_SCORE_TABLE turns them off), 0 when it used the
+ * plain match test, -1 without a context.  Measurement only. */
+int gx_fill_score_table(const gx_context* ctx);
 
 /* Fill launches per pass of the last staged / batch call: 2 when the pairs
  * ran as two groups whose walks overlap the next pass's fills (a batch of
@@ -297,6 +302,16 @@ int gx_twin_admission_mode(const gx_scores* scores, int is_local, int band_waves
  * any other rows_per_lane. */
 int gx_twin_admission_rows(const gx_scores* scores, int is_local, int band_waves, int64_t col_gap,
                            int rows_per_lane, int64_t* bound);
+/* Rows per lane a global staged launch of these pair shapes with planes would
+ * take (host rule only, no device; the rule run_fill itself applies, twin
+ * pairing and int16 admission included): 4 (256-row strips) or 2; 2 also when
+ * the launch would not be the twin fill.  *band_waves (may be NULL) receives
+ * the twin fill's band width, 0 when the launch is not the twin fill.
+ * grid_cap = the device's CU count (0: 256).  GX_TWIN, GX_TWIN_ROWS,
+ * GX_BAND_WAVES, GX_FILL_GRID and GX_LAYOUT act as they do on a launch.  -1 on
+ * invalid scores or shapes (every n and m must be >= 1). */
+int gx_plan_twin_rows(const gx_scores* scores, const int64_t* n, const int64_t* m, size_t npairs, int grid_cap,
+                      int* band_waves);
 /* The fill layout a launch of these pair shapes would take (host rule only,
  * no device): 0 = anti-diagonal 128-row strips (batches), 1 = the column
  * step, 3 = skewed 64-row strips (the latency layouts);

@@ -159,6 +159,17 @@ def edge_batch(kinds=EDGE_KINDS):
     return [fams[s][kinds[k % len(kinds)]] for k, s in enumerate(shapes)]
 
 
+TALL_SHAPES = [(1100, 130), (513, 300)]
+
+
+def edge_batch_rows4(kinds=EDGE_KINDS):
+    """edge_batch() and two taller pairs (a related one of 1,100 x 130 and a
+    random one of 513 x 300) for the fill at four rows a lane
+    (tests/test_gpu_twin_rows4_edges.py): decoders then cross a 256-row strip
+    edge, and at 4-strip bands a band edge (1,100 rows: five strips)."""
+    return edge_batch(kinds) + [edge_family(*TALL_SHAPES[0])["related"], edge_family(*TALL_SHAPES[1])["acgt"]]
+
+
 def _x_ranges(oracle, pairs, scores, is_local):
     lo_s = lo_d = 1 << 60
     hi_s = hi_d = -(1 << 60)
@@ -188,6 +199,18 @@ def test_edge_batches_attain_field_ends(oracle, scores, is_local, alphabet):
     score tables)."""
     kinds = EDGE_KINDS if alphabet == "five_symbols" else tuple(k for k in EDGE_KINDS if k != "acgtn")
     assert _x_ranges(oracle, edge_batch(kinds), scores, is_local) == EDGE_ATTAINED[scores, is_local]
+
+
+@pytest.mark.parametrize("scores", EDGE_SCORES)
+@pytest.mark.parametrize("alphabet", ["five_symbols", "four_symbols"])
+def test_rows4_edge_batches_attain_field_ends(oracle, scores, alphabet):
+    """The enlarged batch of the four-row GPU tests (edge_batch_rows4, global
+    fills only) attains the same ends: the taller pairs stay inside the
+    attained ranges, so both ends of the 5-bit x_S field are still reached."""
+    kinds = EDGE_KINDS if alphabet == "five_symbols" else tuple(k for k in EDGE_KINDS if k != "acgtn")
+    assert _x_ranges(oracle, edge_batch_rows4(kinds), scores, False) == EDGE_ATTAINED[scores, False]
+    if scores in EDGE_SCORES[:2]:
+        assert EDGE_ATTAINED[scores, False][:2] == (-16, 15)
 
 
 def test_field_edge_is_sharp(oracle):

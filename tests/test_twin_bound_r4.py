@@ -19,6 +19,13 @@ every cell's I'', D'', S'' and score_max''; every cell of strip k of every
 256-row-strip band is compared with every base the kernel could hold for it,
 and the largest spread must stay within the per-strip term of the rule.  One
 step past the widest scores the launch must be refused.
+
+Those (1, -1, 0, h) scores leave the bound loose by a factor of 2 to 8.
+HEAVY_CASES below are the scores whose gap extension dominates D: the same
+inputs must reach 0.75 D of the rule there, which is what lets the GPU runs of
+tests/test_gpu_twin_rows4_edges.py load the int16 halves.  Last, the launch's
+rows-per-lane rule (gx_api_plan.cpp twin_plan, through gx_plan_twin_rows) is
+held at each of its thresholds against a restatement in Python.
 """
 import numpy as np
 import pytest
@@ -154,3 +161,191 @@ def test_spread_unequal_twins_rows4(oracle):
     b = bytes(rng.choice(list(b"AC"), size=m).tolist())
     o = oracle.align(a, b, CONFIG_SCORES, want_planes=True)
     assert _max_spread_ratio(o.planes, CONFIG_SCORES[2], W, dm) <= _neighbour_d(CONFIG_SCORES)
+
+
+# ---- scores whose gap extension dominates the neighbour step D ----
+# With h = 0 and a large |g| the worst-input families attain 256 of the 325
+# steps of a strip's term (its rows; 0.787 D), where the (1, -1, 0, h) edge
+# scores above stay below 0.3 D: these are the scores that bring a half-word
+# near its limit, each at the widest width it admits (and the
+# last at W = 3 too, to load that kernel).  All satisfy w16_ok and d8_planes_ok.
+HEAVY_CASES = [((0, -1, -3, 0), 15), ((1, -1, -5, 0), 8), ((1, -1, -6, 0), 7), ((1, -1, -7, 0), 4),
+               ((1, -1, -7, 0), 3)]
+# one step past: (scores, the width refused, the width the launch takes instead)
+ONE_PAST = [((1, -1, -3, 0), 15, 8), ((1, -1, -6, 0), 8, 7), ((1, -1, -7, 0), 7, 4)]
+FAMILIES = ["all_mismatch", "all_match", "gap_rows", "gap_cols", "repeat", "random"]
+WIDER = {3: 4, 4: 7, 7: 8, 8: 15}
+
+
+def widest_admitted(scores, want, dm=0):
+    """twin_width's choice at four rows: the widest instantiated width <= want
+    (3 whatever was asked) whose closed-form bound stays below 30,000; 0: none."""
+    for W in sorted(WIDTHS, reverse=True):
+        if (W <= want or W == 3) and _closed_form(scores, W, dm) < 30000:
+            return W
+    return 0
+
+
+def test_heavy_cases_sit_at_their_widths():
+    """The closed-form bounds the cases were chosen by, and that the plane
+    formats admit them (test_formats restates w16_ok)."""
+    from test_formats import _w16_ok
+    assert [_closed_form(s, W) for s, W in HEAVY_CASES] == [28968, 28414, 29408, 19522, 14722]
+    assert [_closed_form(s, W) for s, W, _ in ONE_PAST] == [33786, 33568, 33922]
+    assert all(_w16_ok(*s) for s, _ in HEAVY_CASES) and all(_w16_ok(*s) for s, _, _ in ONE_PAST)
+    assert max(1, -1) - 2 * (0 - 7) == 15     # (1, -1, -7, 0): x_S reaches the code field's own end
+
+
+@pytest.mark.parametrize("scores,W", HEAVY_CASES)
+def test_heavy_admission_rows4(gx, scores, W):
+    """gx_twin_admission_rows(rows = 4) is the closed form and admits W; the
+    next wider instantiated width refuses these scores (but for the W = 3 row,
+    which repeats the W = 4 scores to run that kernel under load)."""
+    s = gx.Scores(*scores)
+    ok, bound = gx.twin_admission(s, W, 0, rows_per_lane=4)
+    assert bound == _closed_form(scores, W) and ok and bound < 30000, (scores, W, bound)
+    if W != 3:
+        assert widest_admitted(scores, 15) == W
+    if W in (4, 7, 8):     # (15 is the widest instantiated)
+        ok_w, bound_w = gx.twin_admission(s, WIDER[W], 0, rows_per_lane=4)
+        assert bound_w == _closed_form(scores, WIDER[W]) and not ok_w and bound_w >= 30000
+
+
+@pytest.mark.parametrize("scores,refused,takes", ONE_PAST)
+def test_one_past_narrows_on_the_host(gx, monkeypatch, scores, refused, takes):
+    """One step past a width's heaviest scores the admission export refuses
+    it, admits the narrower width, and the launch rule (gx_plan_twin_rows)
+    asked for the refused width takes the narrower one at four rows."""
+    s = gx.Scores(*scores)
+    assert not gx.twin_admission(s, refused, 0, rows_per_lane=4)[0]
+    assert gx.twin_admission(s, takes, 0, rows_per_lane=4)[0]
+    assert widest_admitted(scores, refused) == takes
+    assert all(not gx.twin_admission(s, W, 0, rows_per_lane=4)[0] for W in WIDTHS if takes < W <= refused)
+    _plan_env(monkeypatch, GX_TWIN="1", GX_TWIN_ROWS="4", GX_LAYOUT="0", GX_BAND_WAVES=str(refused))
+    assert gx.plan_twin_rows(s, [(ROWS * refused * 2 + 150, 900)] * 6) == (4, takes)
+
+
+_RATIO = {}
+
+
+def _heavy_ratio(oracle, scores, W, family):
+    """The attained spread ratio of a family at n = 256 W 2 + 150, m = 900, computed once."""
+    key = (scores, W, family)
+    if key not in _RATIO:
+        a, b = _families(ROWS * W * 2 + 150, 900)[family]
+        o = oracle.align(a, b, scores, want_planes=True)
+        _RATIO[key] = _max_spread_ratio(o.planes, scores[2], W, 0)
+    return _RATIO[key]
+
+
+@pytest.mark.parametrize("scores,W", HEAVY_CASES)
+@pytest.mark.parametrize("family", FAMILIES)
+def test_heavy_spread_within_rule(oracle, scores, W, family):
+    """Every state of every 256-row strip stays within the rule's per-strip term."""
+    d = _neighbour_d(scores)
+    ratio = _heavy_ratio(oracle, scores, W, family)
+    assert ratio <= d, (family, scores, W, ratio, d)
+
+
+@pytest.mark.parametrize("scores,W", HEAVY_CASES)
+def test_heavy_spread_loads_the_rule(oracle, scores, W):
+    """... and the families reach at least 0.75 D of it: a strip's rows are
+    256 of the 325 steps of its term (0.787), less a margin for the partial
+    third band.  A property of the oracle and the inputs: it is what lets the
+    GPU runs of these cases (tests/test_gpu_twin_rows4_edges.py) bring the
+    int16 halves near the limit the rule guards."""
+    d = _neighbour_d(scores)
+    ratios = {f: _heavy_ratio(oracle, scores, W, f) for f in FAMILIES}
+    assert max(ratios.values()) >= 0.75 * d, (scores, W, d, ratios)
+
+
+# ---- the rows-per-lane rule of a launch (gx_api_plan.cpp twin_plan, gx_plan_twin_rows) ----
+PLAN_ENV = ("GX_TWIN", "GX_TWIN_ROWS", "GX_BAND_WAVES", "GX_FILL_GRID", "GX_LAYOUT")
+FILL_WIDTHS = (3, 4, 6, 8, 11, 15)    # gx_internal.h kFillWidths
+
+
+def _plan_env(monkeypatch, **env):
+    for k in PLAN_ENV:
+        monkeypatch.delenv(k, raising=False)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def _queue_width(total_strips, grid_cap):
+    """fill_band_waves for short pairs: the narrowest width up to 8 whose
+    bands fit the grid, else 8-strip bands that queue."""
+    for x in FILL_WIDTHS:
+        if x <= 8 and _cdiv(total_strips, x) <= grid_cap:
+            return x
+    return 8
+
+
+def _rows_rule(scores, shapes, grid_cap, env):
+    """The documented rule for a global launch that is the twin fill with
+    twin plane codes: four rows when forced (GX_TWIN_ROWS=4), or unasked when
+    neither band width nor grid is given, every pair has >= 8 strips of 256
+    rows and the twins' strips make >= one 8-strip band per CU; never with
+    GX_TWIN_ROWS=2, without twin codes, or when no width is admitted.  The
+    band width: the one asked for or min(8, the queue rule on the 256-row
+    strips), narrowed to the widest admitted.  Returns (rows, W or None)."""
+    from test_formats import _w16_ok
+    if not _w16_ok(*scores):
+        return 2, None
+    strips4 = [_cdiv(n, ROWS) for n, _ in shapes]
+    twin_strips4 = sum(strips4) // 2
+    force = int(env.get("GX_TWIN_ROWS", "0"))
+    plain = "GX_BAND_WAVES" not in env and "GX_FILL_GRID" not in env
+    auto = plain and min(strips4) >= 8 and _cdiv(twin_strips4, 8) >= grid_cap
+    if force == 2 or not (force == 4 or auto):
+        return 2, None
+    want = int(env["GX_BAND_WAVES"]) if "GX_BAND_WAVES" in env else min(8, _queue_width(twin_strips4, grid_cap))
+    dm = max(m for _, m in shapes) - min(m for _, m in shapes)   # (an upper bound of any twin's gap; 0 below)
+    W = widest_admitted(scores, want, dm)
+    return (4, W) if W else (2, None)
+
+
+SHORT = [(300, 100), (600, 100), (257, 100)]
+
+
+@pytest.mark.parametrize("cap", [256, 100])
+def test_plan_twin_rows_thresholds(gx, monkeypatch, cap):
+    """gx_plan_twin_rows (the function run_fill calls) at each threshold of
+    the rule, the expectation derived from _rows_rule, never read back."""
+    s = gx.Scores(*CONFIG_SCORES)
+    P = 2 * cap                         # pairs of 8 strips: P / 2 twins, one 8-strip band each
+    full = [(2048, 100)] * P
+    # (the big batches take the twin fill unasked: their 128-row-strip bands outnumber 0.9 x the grid)
+    assert 10 * (P // 2) * _cdiv(_cdiv(1792, 128), 8) >= 9 * cap
+
+    def check(shapes, want_rows, want_w=None, scores=CONFIG_SCORES, **env):
+        _plan_env(monkeypatch, **env)
+        assert _rows_rule(scores, shapes, cap, env)[0] == want_rows
+        if want_w is not None:
+            assert _rows_rule(scores, shapes, cap, env)[1] == want_w
+        rows, W = gx.plan_twin_rows(gx.Scores(*scores), shapes, cap)
+        assert rows == want_rows, (shapes[:3], len(shapes), env, rows, W)
+        if want_w is not None:
+            assert W == want_w, (shapes[:3], len(shapes), env, rows, W)
+        return W
+
+    check(full, 4, 8)
+    assert check([(1792, 100)] * P, 2) > 0                       # 7 strips a pair (still the twin fill)
+    check([(1792, 100)] + full[1:], 2)                           # one such pair among the rest
+    check(full[:-2], 2)                                          # cap - 1 bands
+    check(full, 2, GX_BAND_WAVES="8")
+    check(full, 2, GX_FILL_GRID=str(cap))
+    check(full, 2, GX_TWIN_ROWS="2")
+    check(full, 4, 8, GX_TWIN_ROWS="4", GX_BAND_WAVES="8")       # forced: a given width does not matter
+    # small forced launches (GX_TWIN=1 and GX_LAYOUT=0 make three short pairs a layout-0 twin fill)
+    check(SHORT, 4, 3, GX_TWIN="1", GX_LAYOUT="0", GX_TWIN_ROWS="4")
+    check(SHORT, 2, GX_TWIN="1", GX_LAYOUT="0")
+    check(SHORT, 4, 8, GX_TWIN="1", GX_LAYOUT="0", GX_TWIN_ROWS="4", GX_BAND_WAVES="15")
+    check(SHORT, 4, 7, GX_TWIN="1", GX_LAYOUT="0", GX_TWIN_ROWS="4", GX_BAND_WAVES="7")
+    # (1, -1, 0, -20): x_S up to 41, outside the code field: no twin codes, so no four rows
+    check(SHORT, 2, scores=(1, -1, 0, -20), GX_TWIN="1", GX_LAYOUT="0", GX_TWIN_ROWS="4")
+    with pytest.raises(gx.GxError):
+        gx.plan_twin_rows(s, [(0, 100)], cap)
