@@ -297,7 +297,9 @@ struct gx_context {
         void* fdesc = nullptr;               // ... and the fill's descriptor block (run_fill)
         size_t fdesc_cap = 0;
         std::vector<char> fdesc_last;
-    } slots[4];   // 0, 1: pipelined steps by parity (overlapped batches: group A's fills and the walks); 2, 3: group B's fills
+    } slots[6];   // 0, 1: pipelined steps by parity (overlapped batches: group A's fills and the walks); 2, 3: group B's fills;
+                  // the rotating overlapped pipeline (overlap_rotate_plan): fill i's staging in slot 2 (i & 1) + (i / 2 & 1),
+                  // its walk's in slot i % 6
     int last_lay = 0, last_W = 0, last_pbytes = 0;   // the last fill launch (gx_fill_info)
     int last_pbits = 0;                              // ... its plane bits per cell (gx_fill_plane_bits)
     int last_chunks = 1;                             // chunks of the last staged / batch call
@@ -305,6 +307,7 @@ struct gx_context {
     int last_rows = 0;                               // ... its rows per lane (2 or 4; 0: not the twin fill)
     int last_tbl = 0;                                // ... used the small-alphabet score tables (gx_fill_score_table)
     int last_groups = 1;                             // fill launches per pass of the last staged / batch call
+    int last_scheme = 0;                             // ... its overlapped pipeline: 0 none, 1 two A buffers and one B, 2 rotation
     // GX_STAGED_PLANE_SUMS: plane checksums of every pass of a staged run
     DevBuf sums_dev;
     unsigned long long* sums_dst = nullptr;          // where the next fill's checksums go (nullptr: off)
@@ -369,7 +372,9 @@ struct FillJob {
     bool noskel = false;                // nocodes without landing columns: the traceback walks the strips in sequence
     bool local_on = false;              // local (Smith-Waterman) fill: the start cell is the last max (PairRes.lmax_*)
     hipStream_t stream = nullptr;       // the stream its fill runs on (nullptr: the context's)
-    bool plan_only = false;             // run_fill: decide layout and formats only (no buffers, no launch)
+    bool plan_only = false;             // run_fill: decide layout, formats and plane_bytes only (no buffers, no launch)
+    size_t plane_bytes = 0;             // the planes its pairs need
+    size_t plane_floor = 0;             // ... and the least to take from the pool (jobs that rotate over groups of unequal sizes)
     bool table = false;                 // an alignment table (exportable planes: never the twin codes)
     int g = 0;
     double fill_ms = 0.0;
@@ -563,12 +568,25 @@ int copy_steps(const Walk& w, gx_step* steps, size_t cap);
 int label_batch(gx_context* ctx, const std::vector<PairHost>& ph, const HostScores& hs, int is_local, bool track,
                 const std::vector<int>& dev_of, const std::vector<uint64_t>& si,
                 const std::vector<uint64_t>& sj, const std::vector<int64_t>& score,
-                const std::vector<PairRes>& res, const TbOut& tb, double fill_ms, std::vector<Walk>& walks);
+                const std::vector<PairRes>& res, const TbOut& tb, double fill_ms, std::vector<Walk>& walks,
+                const std::vector<const TbOut*>* tb_of = nullptr);
 
 // batches of independent pairs (gx_api_batch.cpp)
 int batch_core_wide(gx_context* ctx, const std::vector<PairHost>& ph,
                     const std::vector<std::pair<const uint8_t*, const uint8_t*>>& proc, const HostScores& hs,
                     int is_local, bool planes, bool track, std::vector<Walk>& walks, double* fill_ms);
+// The rotating overlapped pipeline's index arithmetic (gx_overlap_rotate_plan, gx.h): what fill i = 2 pass + group
+// takes, what its stream waits for on the device and what the host has collected before it is enqueued.
+struct RotatePlan {
+    int job;         // FillJob (plane buffers): i % 3
+    int fslot;       // slot of the fill's staging and events: 2 (i & 1) + (i / 2 & 1), last used by fill i - 4
+    int wslot;       // slot of its walk's staging, events and records: i % 6, last used by walk i - 6
+    int stream;      // fill stream: i & 1
+    int wait_walk;   // the walk whose end event the fill's stream waits for (-1: none): i - 3, the job's last reader
+    int collected;   // the last fill whose results the host collected, and whose buffers it released, before (-1: none): i - 3
+    int labelled;    // the last walk whose records the host collected and labelled before (-1: none)
+};
+RotatePlan overlap_rotate_plan(int i);
 int batch_core_steps(gx_context* ctx, const std::vector<PairHost>& ph,
                      const std::vector<std::pair<const uint8_t*, const uint8_t*>>& proc, const HostScores& hs,
                      const Scores32& sc, int is_local, bool planes, bool track, int nsteps,

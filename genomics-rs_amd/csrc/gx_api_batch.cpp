@@ -139,18 +139,67 @@ static int batch_core(gx_context* ctx, const std::vector<PairHost>& ph,
 // pair, uses a few CUs): the pairs are split into group A (half of them;
 // local batches a fifth) and group B, each filled by its own launch on its
 // own stream.
-// Step k's walk (stream tstream, after both fills) then runs beside step k+1's
-// group-A fill, whose plane codes go to a second A buffer (two A buffers, one
-// B buffer: the device holds P + |A| <= 1.5 P pairs' planes, <= 3 B a cell
-// of twin codes, within the 3.25 B a cell the chunk plan budgets for a pair
-// of a compact-plane batch); step k+1's group-B fill
+//
+// Global batches on the half split rotate three plane buffers
+// (overlap_rotate_plan below).  The fills are numbered i = 2 pass + group and
+// alternate between the two fill streams; fill i runs in FillJob i % 3, and
+// its pairs alone are walked on tstream behind it (the walk waits for that
+// fill's fdone only, so group A's walk of a pass does not wait for group B's
+// fill).  Before fill i is enqueued the host has collected fill i - 3's
+// results and put its buffers back into the pool, and fill i's stream waits on
+// the device for the end of walk i - 3, the last reader of those buffers (the
+// walks share one stream, so that wait covers every earlier walk: any stream
+// may take what the pool holds once it has waited so).  Every device-side
+// wait names work enqueued earlier, with a smaller fill index: fill i waits
+// for walk i - 3, walk i for fill i, and both for their stream predecessors,
+// so the waits cannot form a cycle; inside a launch the band queue's order
+// guarantees progress, and launches do not depend on each other otherwise.
+// In steady state walk i - 3 ended two launches before fill i can start, so
+// no fill waits for a walk (the two-buffer scheme's B fill stood ~5 ms a pass
+// behind the whole pass's walk).  Three consecutive groups are alive at once
+// (A, B, A or B, A, B), every job holding a buffer of the larger group's
+// size: 3 x (Q / 2 + 2) pairs of a Q-pair batch at most, 1.5 P on the
+// headline, 3 x 10 = 1.67 P at Q = 18 (A = 8, B = 10): at 1.5 B a cell of twin
+// codes <= 2.25 + 9 / Q <= 2.82 B a cell of the batch from Q = 16, within the
+// 3.25 B a cell the chunk plan budgets for a pair of a compact-plane batch.
+// The host labels pass k once both its walks are collected, after it has
+// enqueued fill 2k + 4; walk records stay in their slot until then (slot
+// i % 6).  GX_OVERLAP_ROTATE=0 keeps global batches on the scheme below.
+//
+// Local batches (a fifth against four fifths: rotation would hold 1.8 P) and
+// batches split by GX_OVERLAP_A keep two A buffers and one B buffer:
+// step k's walk (stream tstream, after both fills) runs beside step k+1's
+// group-A fill, whose plane codes go to a second A buffer (the device holds
+// P + |A| pairs' planes); step k+1's group-B fill
 // waits on the device for step k's walk before it reuses B's buffers.  Only
 // buffers no pending work uses go back to the pool (a walk's fills after it
 // was collected; B's before its next fill, which waits for the walk that
-// reads them), so any stream may take them.  Returns GX_EAGAIN (nothing
+// reads them), so any stream may take them.  Returns kOverlapNo (nothing
 // left enqueued) when the two groups' fills do not both take the twin fill
 // without landing columns: the caller then runs the plain pipeline.
 static constexpr int kOverlapNo = -1000;
+
+RotatePlan overlap_rotate_plan(int i) {
+    RotatePlan r;
+    r.job = i % 3;
+    r.fslot = 2 * (i & 1) + ((i >> 1) & 1);   // (a stream's two slots: run_fill looks a descriptor block up in slot and slot ^ 1)
+    r.wslot = i % 6;
+    r.stream = i & 1;
+    r.wait_walk = i >= 3 ? i - 3 : -1;
+    r.collected = i >= 3 ? i - 3 : -1;
+    // pass k is labelled after fill 2k + 4 was enqueued: before fill i, the passes up to (i - 5) / 2
+    r.labelled = i >= 5 ? 2 * ((i - 5) / 2) + 1 : -1;
+    return r;
+}
+extern "C" int gx_overlap_rotate_plan(int fill, int* out7) {
+    if (fill < 0 || !out7) return fail(GX_EINVAL, "gx_overlap_rotate_plan: fill < 0 or out is NULL");
+    const RotatePlan r = overlap_rotate_plan(fill);
+    const int v[7] = {r.job, r.fslot, r.wslot, r.stream, r.wait_walk, r.collected, r.labelled};
+    std::copy(v, v + 7, out7);
+    return GX_OK;
+}
+extern "C" int gx_overlap_scheme(const gx_context* ctx) { return ctx ? ctx->last_scheme : -1; }
+
 static int batch_core_overlap(gx_context* ctx, const std::vector<PairHost>& ph,
                               const std::vector<std::pair<const uint8_t*, const uint8_t*>>& proc, const HostScores& hs,
                               const Scores32& sc, int is_local, bool planes, int nsteps, std::vector<Walk>& walks, double* fill_ms,
@@ -233,8 +282,8 @@ static int batch_core_overlap(gx_context* ctx, const std::vector<PairHost>& ph,
         job_release(ctx, jB);
         release_slots(ctx);
     };
+    FillJob pa, pb;
     {   // both groups must take the twin fill without landing columns: decided before anything is enqueued
-        FillJob pa, pb;
         pa.plan_only = pb.plan_only = true;
         int prc = run_fill(ctx, dproc[0][0], dph[0][0], sc, is_local, planes, false, false, pa, chars_dev,
                            chars_dev ? &o1[0][0] : nullptr, chars_dev ? &o2[0][0] : nullptr, &alpha, 0, false);
@@ -244,6 +293,102 @@ static int batch_core_overlap(gx_context* ctx, const std::vector<PairHost>& ph,
         if (prc || !(pa.noskel && pb.noskel && pa.twin && pb.twin && pa.lay == pb.lay && pa.rows == pb.rows)) return kOverlapNo;
     }
     unsigned long long* const sums0 = ctx->sums_dst;
+    const char* rot_e = getenv("GX_OVERLAP_ROTATE");
+    if (!is_local && G == std::max<size_t>(2, ((Q + 1) / 2) & ~(size_t)1) && !(rot_e && !strcmp(rot_e, "0"))) {
+        // the rotation (header comment): three jobs, each with room for the larger group
+        FillJob jobs[3];
+        for (FillJob& j : jobs) j.plane_floor = std::max(pa.plane_bytes, pb.plane_bytes);
+        const int N = 2 * nsteps;
+        std::vector<TbStart> gstarts[2];
+        std::vector<int> gdev(P, -1);   // a pair's index in its group's walk
+        for (int g = 0; g < 2; ++g)
+            for (size_t q = 0; q < gi[g].size(); ++q) {
+                gstarts[g].push_back(TbStart{(int)dph[0][g][q].n, (int)dph[0][g][q].m, 0});
+                gdev[gi[g][q]] = (int)q;
+            }
+        std::vector<const TbOut*> tb_of(P, nullptr);
+        double fms[6] = {0, 0, 0, 0, 0, 0};   // fill i's kernel time, by its walk slot
+        auto drain_r = [&]() {
+            (void)hipStreamSynchronize(sA); (void)hipStreamSynchronize(sB); (void)hipStreamSynchronize(sT);
+            (void)hipStreamSynchronize(ctx->cstream);
+            for (auto& j : jobs) job_release(ctx, j);
+            release_slots(ctx);
+        };
+        auto enqueue = [&](int i) -> int {   // fill i and, behind it, the walk of its pairs
+            const RotatePlan rp = overlap_rotate_plan(i);
+            const int g = i & 1, v = (i >> 1) & 1;
+            FillJob& j = jobs[rp.job];
+            hipStream_t const fs = rp.stream ? sB : sA;
+            if (i == 0) HIPCHK(hipEventRecord(ctx->ev0, fs));
+#ifndef GX_MUT_NO_ROTATE_WAIT   // (mutation build only: the refill no longer ordered behind the job's last walk)
+            if (rp.wait_walk >= 0) HIPCHK(hipStreamWaitEvent(fs, ctx->slots[overlap_rotate_plan(rp.wait_walk).wslot].te, 0));
+#endif
+            j.stream = fs;
+            int r = run_fill(ctx, dproc[v][g], dph[v][g], sc, is_local, planes, false, false, j, chars_dev,
+                             chars_dev ? &o1[v][g] : nullptr, chars_dev ? &o2[v][g] : nullptr, &alpha, rp.fslot, false);
+            if (r) return r;
+            if (!(j.noskel && j.twin && j.lay == pa.lay && j.rows == pa.rows))
+                return i < 2 ? kOverlapNo : fail(GX_EHIP, "overlapped batch: fill formats changed");
+            if (i == N - 1) {   // the last fill's end, behind the one before it on the other stream
+                HIPCHK(hipStreamWaitEvent(fs, ctx->slots[overlap_rotate_plan(i - 1).fslot].fdone, 0));
+                HIPCHK(hipEventRecord(ctx->ev1, fs));
+            }
+            HIPCHK(hipStreamWaitEvent(sT, ctx->slots[rp.fslot].fdone, 0));
+            return run_traceback(ctx, std::vector<const FillJob*>{&j}, gstarts[g], ctx->slots[rp.wslot].out, rp.wslot,
+                                 false, false, sT);
+        };
+        // fill i's results; its buffers back to the pool, though walk i may
+        // still read them: their next user's stream waits for that walk
+        auto collect = [&](int i) -> int {
+            const RotatePlan rp = overlap_rotate_plan(i);
+            FillJob& j = jobs[rp.job];
+            const int r = fill_collect(ctx, j);
+            if (r) return r;
+            fms[rp.wslot] = j.fill_ms;
+            take(j, gi[i & 1]);
+            job_release(ctx, j);
+            return GX_OK;
+        };
+        auto label = [&](int k) -> int {   // pass k: both groups' records, then the labelling
+            const int a = k & 1;
+            for (int g = 0; g < 2; ++g) {
+                const int ws = overlap_rotate_plan(2 * k + g).wslot;
+                const int r = tb_collect(ctx, ws, gi[g].size(), ctx->slots[ws].out);
+                if (r) return r;
+                for (size_t p : gi[g]) tb_of[p] = &ctx->slots[ws].out;
+            }
+            for (size_t p = 0; p < P; ++p)
+                start_cell_common(hs, is_local, ph[p].n, ph[p].m, start_in(res[p]), &si[p], &sj[p], &score[p]);
+            ctx->pass_off = poff[a];
+            const int w0 = overlap_rotate_plan(2 * k).wslot, w1 = overlap_rotate_plan(2 * k + 1).wslot;
+            return label_batch(ctx, *PH[a], hs, is_local, false, gdev, si, sj, score, res, ctx->slots[w0].out,
+                               fms[w0] + fms[w1], *WK[a], &tb_of);
+        };
+        int rc = GX_OK;
+        for (int t = 0; t < N + 3 && !rc; ++t) {
+            if (t >= 3) rc = collect(t - 3);
+            if (!rc && t < N) rc = enqueue(t);
+            if (!rc && t >= 3 && ((t - 3) & 1)) rc = label((t - 3) / 2);
+        }
+        if (!rc) {
+            auto span = [&]() -> int {
+                HIPCHK(hipEventSynchronize(ctx->ev1));
+                float ms = 0.f;
+                HIPCHK(hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1));
+                fsum = ms;
+                return GX_OK;
+            };
+            rc = span();
+        }
+        drain_r();
+        ctx->pass_off = poff[0];
+        if (rc == kOverlapNo) ctx->sums_dst = sums0;   // (the plain pipeline writes this pass's checksums again)
+        if (rc) return rc;
+        ctx->last_groups = 2;
+        ctx->last_scheme = 2;
+        if (fill_ms) *fill_ms = fsum / nsteps;
+        return GX_OK;
+    }
     HIPCHK(hipEventRecord(ctx->ev0, sA));
     int rc = fill(0, 0);
     if (!rc) { rc = fill(1, 0); jb_live = !rc; }
@@ -294,6 +439,7 @@ static int batch_core_overlap(gx_context* ctx, const std::vector<PairHost>& ph,
     ctx->pass_off = poff[0];
     if (rc) return rc;
     ctx->last_groups = 2;
+    ctx->last_scheme = 1;
     if (fill_ms) *fill_ms = fsum / nsteps;
     return GX_OK;
 }
@@ -306,6 +452,7 @@ int batch_core_steps(gx_context* ctx, const std::vector<PairHost>& ph,
                      const SmallAlpha* staged_alpha, const PassSet* alt) {
     const size_t P = ph.size();
     ctx->last_groups = 1;
+    ctx->last_scheme = 0;
     std::vector<size_t> idx;
     for (size_t p = 0; p < P; ++p) if (ph[p].n >= 1 && ph[p].m >= 1) idx.push_back(p);
     // the pair sets by pass parity (one set unless alt)

@@ -230,7 +230,7 @@ void release_held(gx_context* ctx, int slot) {
 // fill_collect or the slot's next fill).
 void release_slots(gx_context* ctx) {
     (void)hipStreamSynchronize(ctx->cstream);
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < (int)(sizeof ctx->slots / sizeof ctx->slots[0]); ++k) {
         release_held(ctx, k);
         pool_put(ctx, ctx->slots[k].held_pres);
     }

@@ -123,7 +123,6 @@ int run_fill(gx_context* ctx, const std::vector<std::pair<const uint8_t*, const 
     ctx->last_pbytes = planes ? (w16 ? 2 : (int)(plane_esz * 3)) : 0;   // (twin codes: 1.5, reported rounded up)
     ctx->last_pbits = planes ? (w16 ? 12 : (int)(plane_esz * 24)) : 0;
     const size_t P = ph.size();
-    if (job.plan_only) { job.twin = twin; return GX_OK; }
     job.pd.assign(P, PairDev{});
     // -- sizes
     size_t chars_bytes = 0, plane_elems = 0, code_elems = 0, feed_recs = 0, prog_elems = 0, skel_elems = 0;
@@ -189,10 +188,14 @@ int run_fill(gx_context* ctx, const std::vector<std::pair<const uint8_t*, const 
     job.total_strips = strips;
     int rc;
     const int nplanes = w16 ? 1 : (lcs && !job.lcs_rows) ? 4 : 3;
+    job.plane_bytes = planes ? plane_elems * plane_esz * nplanes : 0;
+    if (job.plan_only) { job.pd.clear(); return GX_OK; }
     if (!chars_dev) {
         if ((rc = pool_get(ctx, chars_bytes, &job.chars, fs))) return rc;
     }
-    if (planes && (rc = pool_get(ctx, plane_elems * plane_esz * nplanes, &job.planes, fs))) return rc;
+    // (plane_floor: the jobs of the rotating overlapped pipeline hold groups of
+    // unequal sizes in turn, and a buffer of the larger size fits both)
+    if (planes && (rc = pool_get(ctx, std::max(job.plane_bytes, job.plane_floor), &job.planes, fs))) return rc;
     // (no code-word buffer for a fill that stores none: 0.25 B a cell, 21 GB of
     // a 20-pair 64k chunk, which the overlapped pipeline's second A group needs)
     const bool want_codes = codes && !job.nocodes;

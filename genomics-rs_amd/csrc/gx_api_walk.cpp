@@ -341,18 +341,22 @@ int copy_steps(const Walk& w, gx_step* steps, size_t cap) {
 
 // Labels one batch's walks (host, algo.rs:339-422), pairs on the worker pool:
 // interior moves from the device's row records (dev_of[p] >= 0), then the
-// analytic boundary; fills walks[p].res.
+// analytic boundary; fills walks[p].res.  tb_of: the pairs' records come from
+// several walks (one per fill group): pair p's from (*tb_of)[p], where
+// dev_of[p] is its index in that walk.
 int label_batch(gx_context* ctx, const std::vector<PairHost>& ph, const HostScores& hs, int is_local, bool track,
                 const std::vector<int>& dev_of, const std::vector<uint64_t>& si,
                 const std::vector<uint64_t>& sj, const std::vector<int64_t>& score,
-                const std::vector<PairRes>& res, const TbOut& tb, double fill_ms, std::vector<Walk>& walks) {
+                const std::vector<PairRes>& res, const TbOut& tb, double fill_ms, std::vector<Walk>& walks,
+                const std::vector<const TbOut*>* tb_of) {
     const size_t P = ph.size();
     walks.resize(P);   // keeps the step buffers of a reused vector
     std::vector<int> prc(P, GX_OK);
     std::vector<std::string> perr(P);
+    auto tb_for = [&](size_t p) -> const TbOut& { return tb_of && (*tb_of)[p] ? *(*tb_of)[p] : tb; };
     const std::function<void(size_t)> label_one = [&](size_t p) {
         if (dev_of[p] >= 0)
-            prc[p] = label_walk_records(hs, is_local, ph[p].s1, ph[p].n, ph[p].s2, ph[p].m, si[p], sj[p], tb,
+            prc[p] = label_walk_records(hs, is_local, ph[p].s1, ph[p].n, ph[p].s2, ph[p].m, si[p], sj[p], tb_for(p),
                                         (size_t)dev_of[p], walks[p]);
         else
             prc[p] = label_walk(hs, is_local, ph[p].s1, ph[p].n, ph[p].s2, ph[p].m, si[p], sj[p], 0,
@@ -381,7 +385,7 @@ int label_batch(gx_context* ctx, const std::vector<PairHost>& ph, const HostScor
         w.res.max_cell_j = interior ? (uint64_t)res[p].max_j : 0;
         w.res.matches_at_max = interior ? (uint64_t)res[p].mam : 0;
         w.res.fill_us = (int64_t)(fill_ms * 1000.0);
-        w.res.retrace_us = (int64_t)(tb.ms * 1000.0);
+        w.res.retrace_us = (int64_t)(tb_for(p).ms * 1000.0);
     }
     if (ctx->pass_rec) {   // a staged run keeps every pass's results (this chunk's pairs)
         const size_t base = (size_t)ctx->pass_k * ctx->pass_P + ctx->pass_off;

@@ -87,7 +87,7 @@ EXPORTED = ["gx_last_error", "gx_version", "gx_context_create", "gx_context_dest
             "gx_table_plane_sums", "gx_retrace", "gx_table_free", "gx_align", "gx_align_batch", "gx_align_batch_multi",
             "gx_stage_pairs",
             "gx_run_staged", "gx_run_staged_steps", "gx_staged_plane_sums", "gx_staged_steps",
-            "gx_staged_pass_results", "gx_fill_info", "gx_batch_chunks", "gx_fill_twin", "gx_fill_groups", "gx_fill_plane_bits", "gx_plane_bytes_per_cell", "gx_twin_admission",
+            "gx_staged_pass_results", "gx_fill_info", "gx_batch_chunks", "gx_fill_twin", "gx_fill_groups", "gx_overlap_scheme", "gx_overlap_rotate_plan", "gx_fill_plane_bits", "gx_plane_bytes_per_cell", "gx_twin_admission",
             "gx_twin_admission_mode", "gx_twin_admission_rows", "gx_fill_rows", "gx_fill_score_table", "gx_plan_layout",
             "gx_plan_twin_rows", "gx_staged_table",
             "gx_fasta_load",
@@ -145,6 +145,9 @@ def lib():
     L.gx_batch_chunks.argtypes = [vp]
     L.gx_fill_twin.argtypes = [vp]
     L.gx_fill_groups.argtypes = [vp]
+    if hasattr(L, "gx_overlap_scheme"):   # (absent from builds before the rotating pipeline, run for A/B timing)
+        L.gx_overlap_scheme.argtypes = [vp]
+        L.gx_overlap_rotate_plan.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_int)]
     if hasattr(L, "gx_fill_plane_bits"):   # (absent from pre-12-bit builds run for A/B timing)
         L.gx_fill_plane_bits.argtypes = [vp]
     L.gx_plane_bytes_per_cell.argtypes = [ctypes.POINTER(CScores), ctypes.c_int]
@@ -426,11 +429,27 @@ class Context:
                 "twin_rows": lib().gx_fill_rows(self.ptr) if hasattr(lib(), "gx_fill_rows") else 2,
                 "score_table": lib().gx_fill_score_table(self.ptr) if hasattr(lib(), "gx_fill_score_table") else -1}
 
+    def overlap_scheme(self) -> int:
+        """Which overlapped pipeline the last staged / batch call ran (gx_overlap_scheme):
+        2 the three-buffer rotation, 1 two A buffers and one B buffer, 0 none."""
+        return lib().gx_overlap_scheme(self.ptr)
+
     def __del__(self):
         try:
             self.close()
         except Exception:
             pass
+
+
+ROTATE_PLAN_FIELDS = ("job", "fslot", "wslot", "stream", "wait_walk", "collected", "labelled")
+
+
+def overlap_rotate_plan(fill: int) -> dict:
+    """The rotating overlapped pipeline's index arithmetic for fill 2 pass + group
+    (gx_overlap_rotate_plan; host only)."""
+    v = (ctypes.c_int * 7)()
+    _check(lib().gx_overlap_rotate_plan(fill, v))
+    return dict(zip(ROTATE_PLAN_FIELDS, (int(x) for x in v)))
 
 
 _default_ctx: dict = {}

@@ -274,6 +274,17 @@ int gx_fill_score_table(const gx_context* ctx);
  * ran as two groups whose walks overlap the next pass's fills (a batch of
  * long pairs on the twin fill), else 1. */
 int gx_fill_groups(const gx_context* ctx);
+/* Which overlapped pipeline the last staged / batch call ran: 2 the rotation
+ * of three plane buffers (global batches split in halves; GX_OVERLAP_ROTATE=0
+ * turns it off), 1 two group-A buffers and one group-B buffer (local batches,
+ * GX_OVERLAP_A splits), 0 none (gx_fill_groups 1), -1 without a context. */
+int gx_overlap_scheme(const gx_context* ctx);
+/* The rotation's index arithmetic for fill number `fill` = 2 pass + group
+ * (host only, no device call).  out7: the FillJob it fills (fill % 3), its
+ * fill slot, its walk slot, its stream (0 / 1), the walk whose end its stream
+ * waits for on the device (-1: none), the last fill the host has collected
+ * and the last walk it has labelled before it enqueues this fill (-1: none). */
+int gx_overlap_rotate_plan(int fill, int* out7);
 /* Score-plane bytes per cell a batch launch (layout 0, no max tracking)
  * writes with these scores: 3 when the compact format's range proof holds
  * (global mode, g, h <= 0, differences within a signed byte), else 12; -1 on

@@ -4,7 +4,7 @@ pipeline of the K timed passes, bench.py) can be recomputed from a tracked
 file.
 
     python tools/pass_summary.py KERNEL_TRACE.csv --passes K [--kernel fill_pk_kernel]
-                                 [--cells CELLS_PER_PASS] [--out profiles/x.json]
+                                 [--also tb_seq_kernel] [--cells CELLS_PER_PASS] [--out profiles/x.json]
 
 The profiled command must end its fill launches with the K timed passes
 (bench.py ... --no-verify --int32-steps 0 --no-plane-steps 0
@@ -27,6 +27,8 @@ def main():
     ap.add_argument("--cells", type=float, default=0.0, help="DP cells per pass (GCUPS column)")
     ap.add_argument("--skip", type=int, default=-1,
                     help="fill launches before the timed call (default: all but the last passes x G)")
+    ap.add_argument("--also", default="", help="list this kernel's launches too (substring, e.g. tb_seq_kernel) and "
+                                               "how much of each gap between a stream's fills one of them covers")
     ap.add_argument("--out")
     a = ap.parse_args()
     rows = [r for r in csv.DictReader(open(a.trace)) if a.kernel in r["Kernel_Name"]]
@@ -59,6 +61,33 @@ def main():
         st = [int(r["Start_Timestamp"]) for r in b]
         if len(st) > 1:
             out["pass_period_ms"] = round(statistics.mean((st[k + 1] - st[k]) / 1e6 for k in range(len(st) - 1)), 3)
+            # (the median leaves out a call's first interval: its first two fills start together, and the
+            # half-pass stagger between the streams settles only after them)
+            out["pass_period_median_ms"] = round(statistics.median((st[k + 1] - st[k]) / 1e6 for k in range(len(st) - 1)), 3)
+    # the gaps between consecutive timed launches of each stream (end -> next start)
+    ts = lambda r, k: (int(r[k]) - t0) / 1e6
+    also = []
+    if a.also:   # another kernel's launches in the timed window (the walk: --also tb_seq_kernel)
+        t1 = max(int(r["End_Timestamp"]) for r in timed)
+        also = sorted((r for r in csv.DictReader(open(a.trace))
+                       if a.also in r["Kernel_Name"] and t0 <= int(r["Start_Timestamp"]) <= t1),
+                      key=lambda r: int(r["Start_Timestamp"]))
+        out["also_kernel"] = a.also
+        out["also_launches"] = [{"stream": r["Stream_Id"], "start_ms": round(ts(r, "Start_Timestamp"), 3),
+                                 "duration_ms": round(dur(r), 3)} for r in also]
+    gaps = {}
+    for s, v in per_stream.items():
+        g = []
+        for x, y in zip(v, v[1:]):
+            e, b = ts(x, "End_Timestamp"), ts(y, "Start_Timestamp")
+            rec = {"from_ms": round(e, 3), "gap_ms": round(b - e, 3)}
+            if also:   # how much of the gap one of the other kernel's launches covers
+                rec["covered_by_also_ms"] = round(max([0.0] + [min(b, ts(w, "End_Timestamp")) - max(e, ts(w, "Start_Timestamp"))
+                                                              for w in also]), 3)
+            g.append(rec)
+        gaps[s] = g
+    out["stream_gaps"] = gaps
+    out["stream_gap_mean_ms"] = {s: round(statistics.mean(x["gap_ms"] for x in g), 3) for s, g in gaps.items() if g}
     if a.cells:
         out["fill_gcups_per_pass"] = round(a.cells / (out["pipeline_ms_per_pass"] * 1e-3) / 1e9, 1)
     print(json.dumps(out, indent=1))
