@@ -123,13 +123,12 @@ static int pool_take(gx_context* ctx, size_t bytes, DevBuf* out) {
 // overlapped pipeline's next fill and the walk still reading its planes) has
 // those readers read garbage.  Poisoning at release instead would have to run
 // on the last reader's stream and order every later user behind it.
+// Read at every request, not once a process: a test that sets it after the
+// process's first launch (every poisoned variant of the suite but the first
+// test of a run) would otherwise run unpoisoned without saying so.
 static bool pool_poison() {
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("GX_POOL_POISON");
-        v = (e && *e && strcmp(e, "0")) ? 1 : 0;
-    }
-    return v == 1;
+    const char* e = getenv("GX_POOL_POISON");
+    return e && *e && strcmp(e, "0");
 }
 void pool_put(gx_context* ctx, DevBuf& b) {
     if (b.p) ctx->free_list.push_back(b);
