@@ -9,7 +9,7 @@
 //   gx_api_staged.cpp   device-resident (staged) batches, the benchmark path
 //   gx_api_compare.cpp  compare mode: longest-common-substring recursion (main.rs:216-379)
 //   gx_api_suffix.cpp   suffix-tree mode: BWT and tree statistics from the suffix array (main.rs:154-215)
-//   gx_api_search.cpp   search mode: a kept suffix index and batched exact-match queries on it
+//   gx_api_search.cpp   search mode: a kept suffix index and batched exact-match and k-mismatch queries on it
 // Not a public header: host code only, one library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -338,6 +338,9 @@ struct gx_context {
     // the last search (gx_search_info; gx_api_search.cpp)
     uint64_t srch_words = 0;
     double srch_ms = 0.0, srch_locate_ms = 0.0;
+    // the last approximate search (gx_approx_info; gx_api_search.cpp)
+    uint64_t aprx_cands = 0, aprx_words = 0;
+    double aprx_seed_ms = 0.0, aprx_verify_ms = 0.0;
 };
 
 struct PairHost {

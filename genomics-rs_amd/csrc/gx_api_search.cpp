@@ -1,5 +1,6 @@
 // gx_api_search.cpp -- search mode: a suffix index that outlives the call and
-// batched exact-match queries on it.  No counterpart in the
+// batched exact-match queries on it, and queries with at most k
+// substitutions.  No counterpart in the
 // reference's main.rs; it consumes the suffix array suffix-tree mode builds.
 //
 //   index build    text to device text + device suffix array (suffix_device_sa,
@@ -12,7 +13,12 @@
 //   device search  stage patterns and offsets, interval kernel, and for
 //                  positions clamp, exclusive scan and gather (gx_search.hip);
 //                  the per-pattern ascending sort is the host's
+//   approximate    both sides: the k + 1 pieces of every pattern through the
+//                  exact search (the seeds), the seed hits summed in 64 bits and
+//                  held against GX_APPROX_CAND_BUDGET, then the verify walk of
+//                  gx_approx.h on every seed hit.  Device: gx_approx.hip
 #include "gx_api.h"
+#include "gx_approx.h"
 #include "gx_search.h"
 
 struct gx_suffix_index {
@@ -27,8 +33,9 @@ namespace {
 
 static_assert(sizeof(gx_search_hit) == sizeof(SrchHit), "gx_search_hit layout");
 
-// hit_offsets from hits; returns the total.
-uint64_t offsets_of(const gx_search_hit* hits, size_t npat, uint32_t max_hits, uint64_t* hit_offsets) {
+// hit_offsets from hits (gx_search_hit or gx_approx_hit); returns the total.
+template <class Hit>
+uint64_t offsets_of(const Hit* hits, size_t npat, uint32_t max_hits, uint64_t* hit_offsets) {
     uint64_t tot = 0;
     for (size_t p = 0; p < npat; ++p) {
         if (hit_offsets) hit_offsets[p] = tot;
@@ -185,6 +192,277 @@ int search_device(gx_suffix_index* idx, const uint8_t* pats, size_t total_bytes,
     return GX_OK;
 }
 
+// What both searches refuse of a batch before a pattern byte is staged.
+int check_batch(const uint8_t* patterns, const uint64_t* offsets, size_t npat) {
+    if (offsets[0] != 0) return fail(GX_EINVAL, "offsets[0] is not 0");
+    for (size_t p = 0; p < npat; ++p) {
+        if (offsets[p + 1] < offsets[p])
+            return fail(GX_EINVAL, "offsets decrease at pattern " + std::to_string(p));
+        if (offsets[p + 1] - offsets[p] > kSrchMaxPattern)
+            return fail(GX_ERANGE, "pattern " + std::to_string(p) + " has " + std::to_string(offsets[p + 1] - offsets[p]) +
+                                       " bytes, more than 65535");
+    }
+    const uint64_t total_bytes = offsets[npat];
+    // (one more than the 32-bit device offsets need, for the scan's npat + 1 entries and its tile rounding)
+    if (total_bytes + npat >= (1ull << 32) || (uint64_t)npat + 1 + kSufTile >= (1ull << 32))
+        return fail(GX_ERANGE, "search: pattern bytes plus patterns come to " + std::to_string(total_bytes + npat) +
+                                   ", 2^32 or more: split the batch or lower max_hits");
+    if (total_bytes && !patterns) return fail(GX_EINVAL, "patterns is NULL");
+    // (one flat pass the compiler vectorises; the culprit is looked for only when there is one)
+    unsigned low = 0;
+    for (uint64_t k = 0; k < total_bytes; ++k) low |= patterns[k] <= 0x24;
+    for (size_t p = 0; low && p < npat; ++p)
+        for (uint64_t k = offsets[p]; k < offsets[p + 1]; ++k)
+            if (patterns[k] <= 0x24)
+                return fail(GX_EINVAL, "pattern " + std::to_string(p) + ": byte " + std::to_string((int)patterns[k]) +
+                                           " at offset " + std::to_string(k - offsets[p]) + " is not above '$'");
+    return GX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// k mismatches: pigeonhole seeds through the exact search, then
+// the verify walk of gx_approx.h on every seed hit, host and device alike
+
+static_assert(sizeof(gx_approx_hit) == sizeof(AprxHit), "gx_approx_hit layout");
+static_assert(GX_APPROX_MAX_K == kAprxMaxK, "GX_APPROX_MAX_K");
+
+// GX_APPROX_CAND_BUDGET, read on every call: seed hits a batch may have.
+uint64_t approx_budget() {
+    uint64_t b = 1ull << 27;
+    if (const char* e = getenv("GX_APPROX_CAND_BUDGET")) {
+        char* end = nullptr;
+        const unsigned long long v = strtoull(e, &end, 10);
+        if (end != e && v > 0) b = v;
+    }
+    return std::min<uint64_t>(b, 1ull << 31);
+}
+
+int budget_error(uint64_t total, uint64_t budget) {
+    return fail(GX_ERANGE, "approximate search: " + std::to_string(total) + " seed hits, more than GX_APPROX_CAND_BUDGET = " +
+                               std::to_string(budget) + ": split the batch, lower k, or raise GX_APPROX_CAND_BUDGET");
+}
+
+// The budget refusal's only output: candidates per pattern from the pieces' intervals.
+void candidates_only(const SrchHit* ph, size_t npat, uint32_t k1, gx_approx_hit* hits) {
+    for (size_t p = 0; p < npat; ++p) {
+        uint64_t c = 0;
+        for (uint32_t j = 0; j < k1; ++j) c += ph[p * k1 + j].count;
+        hits[p].candidates = (uint32_t)std::min<uint64_t>(c, 0xFFFFFFFFull);
+    }
+}
+
+// Each pattern's (position, distance) pairs ascending by position (positions are distinct within a pattern).
+void sort_pairs(uint32_t* positions, uint8_t* distances, const uint64_t* hit_offsets, size_t npat) {
+    std::vector<uint64_t> tmp;
+    for (size_t p = 0; p < npat; ++p) {
+        const uint64_t b = hit_offsets[p], len = hit_offsets[p + 1] - b;
+        if (len < 2) continue;
+        tmp.resize(len);
+        for (uint64_t i = 0; i < len; ++i) tmp[i] = (uint64_t)positions[b + i] << 8 | distances[b + i];
+        std::sort(tmp.begin(), tmp.end());
+        for (uint64_t i = 0; i < len; ++i) {
+            positions[b + i] = (uint32_t)(tmp[i] >> 8);
+            distances[b + i] = (uint8_t)tmp[i];
+        }
+    }
+}
+
+// pats: padded as for search_host.
+int approx_host(const gx_suffix_index* idx, const uint8_t* pats, const uint32_t* offs, size_t npat, uint32_t k,
+                gx_approx_hit* hits, uint32_t max_hits, uint32_t* positions, uint8_t* distances, size_t cap,
+                uint64_t* hit_offsets) {
+    const uint32_t n = (uint32_t)idx->n, N = n + 1, k1 = k + 1;
+    const uint8_t* t = idx->text.data();
+    const uint32_t* sa = idx->sa.data();
+    // seeds: every piece through the exact search, in candidate order
+    std::vector<SrchHit> ph(npat * k1);
+    uint64_t words = 0, total = 0;
+    for (size_t p = 0; p < npat; ++p) {
+        const uint32_t m = offs[p + 1] - offs[p];
+        for (uint32_t j = 0; j < k1; ++j) {
+            const uint32_t ps = aprx_piece_start(m, k1, j), pe = aprx_piece_start(m, k1, j + 1);
+            ph[p * k1 + j] = srch_one(t, sa, N, pats + offs[p] + ps, pe - ps, &words);
+            total += ph[p * k1 + j].count;
+        }
+    }
+    const uint64_t budget = approx_budget();
+    if (total > budget) {
+        candidates_only(ph.data(), npat, k1, hits);
+        return budget_error(total, budget);
+    }
+    std::vector<uint64_t> out;   // position << 8 | distance, the reported ones of every pattern in turn
+    for (size_t p = 0; p < npat; ++p) {
+        const uint32_t m = offs[p + 1] - offs[p];
+        const uint8_t* P = pats + offs[p];
+        gx_approx_hit h{0, 0xFFFFFFFFu, 0, 0};
+        uint64_t best = ~0ull;
+        for (uint32_t j = 0; j < k1; ++j) {
+            const SrchHit& s = ph[p * k1 + j];
+            const uint32_t ps = aprx_piece_start(m, k1, j);
+            h.candidates += s.count;
+            for (uint32_t r = 0; r < s.count; ++r) {
+                const uint32_t at = sa[s.lo + r];
+                if (at < ps || (uint64_t)(at - ps) + m > n) continue;   // the window leaves the text
+                const uint32_t c = at - ps;
+                uint32_t d = 0;
+                if (!aprx_verify(t + c, P, m, k, j, &d, &words)) continue;
+                best = std::min(best, (uint64_t)d << 32 | c);
+                if (positions && h.count < max_hits) out.push_back((uint64_t)c << 8 | d);
+                ++h.count;
+            }
+        }
+        if (h.count) {
+            h.best_dist = (uint32_t)(best >> 32);
+            h.best_pos = (uint32_t)best;
+        }
+        hits[p] = h;
+    }
+    if (!positions) {
+        if (hit_offsets) offsets_of(hits, npat, max_hits, hit_offsets);
+        return GX_OK;
+    }
+    const uint64_t total_out = offsets_of(hits, npat, max_hits, hit_offsets);
+    if (total_out > cap) return cap_error(total_out, cap);
+    for (uint64_t i = 0; i < total_out; ++i) {
+        positions[i] = (uint32_t)(out[i] >> 8);
+        distances[i] = (uint8_t)out[i];
+    }
+    sort_pairs(positions, distances, hit_offsets, npat);
+    return GX_OK;
+}
+
+// pats: unpadded, as for search_device.  Takes ctx->mu.
+int approx_device(gx_suffix_index* idx, const uint8_t* pats, size_t total_bytes, const uint32_t* offs, uint32_t npat,
+                  uint32_t k, gx_approx_hit* hits, uint32_t max_hits, uint32_t* positions, uint8_t* distances, size_t cap,
+                  uint64_t* hit_offsets) {
+    gx_context* ctx = idx->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint32_t N = (uint32_t)idx->n + 1, k1 = k + 1, npieces = npat * k1;
+    ctx->aprx_cands = ctx->aprx_words = 0;
+    ctx->aprx_seed_ms = ctx->aprx_verify_ms = 0.0;
+    DevBuf d_pat, d_off, d_poff, d_phits, d_coff, d_tmp, d_small, d_keep, d_ktmp, d_dist, d_start, d_best, d_hits, d_oq,
+        d_pos, d_dst;
+    auto done = [&](int rc) {
+        if (rc != GX_OK) (void)hipStreamSynchronize(st);   // nothing of this call still runs on the buffers
+        for (DevBuf* b : {&d_pat, &d_off, &d_poff, &d_phits, &d_coff, &d_tmp, &d_small, &d_keep, &d_ktmp, &d_dist,
+                          &d_start, &d_best, &d_hits, &d_oq, &d_pos, &d_dst})
+            pool_put(ctx, *b);
+        return rc;
+    };
+#define SR_TRY(expr)                                                                                          \
+    do {                                                                                                      \
+        hipError_t e_ = (expr);                                                                               \
+        if (e_ != hipSuccess)                                                                                 \
+            return done(fail(e_ == hipErrorOutOfMemory ? GX_ENOMEM : GX_EHIP,                                 \
+                             std::string(#expr) + ": " + hipGetErrorString(e_)));                             \
+    } while (0)
+#define SR_GET(buf, bytes)                                                      \
+    do {                                                                        \
+        const int rc_ = pool_get(ctx, (bytes), &(buf), st);                     \
+        if (rc_ != GX_OK) return done(rc_);                                     \
+    } while (0)
+    // patterns and offsets as the exact search stages them; the piece offsets are the device's own
+    SR_GET(d_pat, total_bytes + kSufPad);
+    SR_GET(d_off, ((size_t)npat + 1) * 4);
+    SR_GET(d_poff, ((size_t)npieces + 1) * 4);
+    SR_GET(d_phits, (size_t)npieces * sizeof(SrchHit));
+    SR_GET(d_coff, ((size_t)npieces + 1) * 4);
+    SR_GET(d_tmp, suf_tiles((size_t)npieces + 1) * 4);
+    SR_GET(d_small, 64);
+    unsigned long long* d_cnt = (unsigned long long*)d_small.p;   // [0] seed word steps, [1] seed hits, [2] verify word steps
+    SR_TRY(hipMemcpyAsync(d_pat.p, pats, total_bytes, hipMemcpyHostToDevice, st));
+    SR_TRY(hipMemsetAsync((uint8_t*)d_pat.p + total_bytes, 0, kSufPad, st));
+    SR_TRY(hipMemcpyAsync(d_off.p, offs, ((size_t)npat + 1) * 4, hipMemcpyHostToDevice, st));
+    SR_TRY(hipMemsetAsync(d_cnt, 0, 24, st));
+    const uint8_t* text = (const uint8_t*)idx->d_text.p;
+    const uint32_t* sa = (const uint32_t*)idx->d_sa.p;
+    const uint8_t* dp = (const uint8_t*)d_pat.p;
+    const uint32_t* off = (const uint32_t*)d_off.p;
+    uint32_t* poff = (uint32_t*)d_poff.p;
+    SrchHit* ph = (SrchHit*)d_phits.p;
+    uint32_t* coff = (uint32_t*)d_coff.p;
+    // stages 1 to 4: pieces, seeds, their 64-bit total, candidate offsets.  The scan is 32-bit and is
+    // relied upon only once the host has held the total against the budget.
+    SR_TRY(hipEventRecord(ctx->ev0, st));
+    SR_TRY(launch_aprx_pieces(off, npat, k1, poff, st));
+    SR_TRY(launch_srch_range(text, sa, N, dp, poff, npieces, ph, d_cnt, st));
+    SR_TRY(launch_aprx_total(ph, npieces, d_cnt + 1, st));
+    SR_TRY(launch_srch_clamp(ph, npieces, 0xFFFFFFFFu, coff, st));
+    SR_TRY(launch_suf_scan(coff, npieces + 1, false, (uint32_t*)d_tmp.p, st));
+    SR_TRY(hipEventRecord(ctx->ev1, st));
+    unsigned long long* pin = (unsigned long long*)io_pinned(ctx, 128);
+    if (!pin) return done(fail(GX_ENOMEM, "approximate search: pinned staging"));
+    SR_TRY(hipMemcpyAsync(pin, d_cnt, 16, hipMemcpyDeviceToHost, st));
+    SR_TRY(hipStreamSynchronize(st));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) ctx->aprx_seed_ms = ms;
+    const uint64_t total = pin[1], budget = approx_budget();
+    ctx->aprx_cands = total;
+    if (total > budget) {
+        std::vector<SrchHit> hp(npieces);
+        SR_TRY(hipMemcpyAsync(hp.data(), ph, (size_t)npieces * sizeof(SrchHit), hipMemcpyDeviceToHost, st));
+        SR_TRY(hipStreamSynchronize(st));
+        candidates_only(hp.data(), npat, k1, hits);
+        return done(budget_error(total, budget));
+    }
+    // stages 5 and 6: verify, compact
+    const uint32_t T = (uint32_t)total;   // <= 2^31
+    const uint64_t dev_cap =
+        positions ? std::min<uint64_t>(std::min<uint64_t>(cap, total), (uint64_t)npat * std::min(max_hits, N)) : 0;
+    SR_GET(d_keep, ((size_t)T + 1) * 4);
+    SR_GET(d_ktmp, suf_tiles((size_t)T + 1) * 4);
+    SR_GET(d_dist, std::max<size_t>(T, 1));
+    SR_GET(d_start, std::max<size_t>(T, 1) * 4);
+    SR_GET(d_best, (size_t)npat * 8);
+    SR_GET(d_hits, (size_t)npat * sizeof(AprxHit));
+    SR_GET(d_oq, ((size_t)npat + 1) * 4);
+    if (dev_cap) {
+        SR_GET(d_pos, (size_t)dev_cap * 4);
+        SR_GET(d_dst, (size_t)dev_cap);
+    }
+    uint32_t* keep = (uint32_t*)d_keep.p;
+    uint32_t* oq = (uint32_t*)d_oq.p;
+    SR_TRY(hipMemsetAsync(d_best.p, 0xFF, (size_t)npat * 8, st));
+    SR_TRY(hipEventRecord(ctx->ev1, st));
+    SR_TRY(launch_aprx_verify(text, sa, N, dp, off, poff, ph, coff, npieces, k, T, keep, (uint8_t*)d_dist.p,
+                              (uint32_t*)d_start.p, (unsigned long long*)d_best.p, d_cnt + 2, st));
+    SR_TRY(launch_suf_scan(keep, T + 1, false, (uint32_t*)d_ktmp.p, st));
+    SR_TRY(launch_aprx_fill(coff, keep, (const unsigned long long*)d_best.p, npat, k1, max_hits, (AprxHit*)d_hits.p, oq,
+                            st));
+    if (dev_cap) {
+        SR_TRY(launch_suf_scan(oq, npat + 1, false, (uint32_t*)d_tmp.p, st));
+        SR_TRY(launch_aprx_scatter(coff, keep, oq, npat, k1, T, max_hits, (const uint32_t*)d_start.p,
+                                   (const uint8_t*)d_dist.p, (uint32_t*)d_pos.p, (uint8_t*)d_dst.p, dev_cap, st));
+    }
+    SR_TRY(hipEventRecord(ctx->ev2, st));
+    // (behind the last event: the events time kernels alone)
+    SR_TRY(hipMemcpyAsync(pin + 2, d_cnt + 2, 8, hipMemcpyDeviceToHost, st));
+    SR_TRY(hipMemcpyAsync(hits, d_hits.p, (size_t)npat * sizeof(AprxHit), hipMemcpyDeviceToHost, st));
+    SR_TRY(hipStreamSynchronize(st));
+    if (hipEventElapsedTime(&ms, ctx->ev1, ctx->ev2) == hipSuccess) ctx->aprx_verify_ms = ms;
+    ctx->aprx_words = pin[2];
+    if (!positions) {
+        if (hit_offsets) offsets_of(hits, npat, max_hits, hit_offsets);
+        return done(GX_OK);
+    }
+    // the positions: their number is known to the host only now, so that GX_ECAP leaves positions[] and
+    // distances[] untouched and the copies move no more than them (a total above dev_cap is above cap)
+    const uint64_t total_out = offsets_of(hits, npat, max_hits, hit_offsets);
+    if (total_out > cap) return done(cap_error(total_out, cap));
+    if (total_out) {
+        SR_TRY(hipMemcpyAsync(positions, d_pos.p, (size_t)total_out * 4, hipMemcpyDeviceToHost, st));
+        SR_TRY(hipMemcpyAsync(distances, d_dst.p, (size_t)total_out, hipMemcpyDeviceToHost, st));
+        SR_TRY(hipStreamSynchronize(st));
+    }
+    done(GX_OK);   // (the stream is idle)
+#undef SR_TRY
+#undef SR_GET
+    sort_pairs(positions, distances, hit_offsets, npat);
+    return GX_OK;
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -291,28 +569,9 @@ extern "C" int gx_suffix_index_search(gx_suffix_index* idx, const uint8_t* patte
     if (!offsets) return fail(GX_EINVAL, "offsets is NULL");
     if (npat && !hits) return fail(GX_EINVAL, "hits is NULL");
     if (positions && !hit_offsets) return fail(GX_EINVAL, "hit_offsets is NULL with positions");
-    if (offsets[0] != 0) return fail(GX_EINVAL, "offsets[0] is not 0");
-    for (size_t p = 0; p < npat; ++p) {
-        if (offsets[p + 1] < offsets[p])
-            return fail(GX_EINVAL, "offsets decrease at pattern " + std::to_string(p));
-        if (offsets[p + 1] - offsets[p] > kSrchMaxPattern)
-            return fail(GX_ERANGE, "pattern " + std::to_string(p) + " has " + std::to_string(offsets[p + 1] - offsets[p]) +
-                                       " bytes, more than 65535");
-    }
+    const int brc = check_batch(patterns, offsets, npat);
+    if (brc != GX_OK) return brc;
     const uint64_t total_bytes = offsets[npat];
-    // (one more than the 32-bit device offsets need, for the scan's npat + 1 entries and its tile rounding)
-    if (total_bytes + npat >= (1ull << 32) || (uint64_t)npat + 1 + kSufTile >= (1ull << 32))
-        return fail(GX_ERANGE, "search: pattern bytes plus patterns come to " + std::to_string(total_bytes + npat) +
-                                   ", 2^32 or more: split the batch or lower max_hits");
-    if (total_bytes && !patterns) return fail(GX_EINVAL, "patterns is NULL");
-    // (one flat pass the compiler vectorises; the culprit is looked for only when there is one)
-    unsigned low = 0;
-    for (uint64_t k = 0; k < total_bytes; ++k) low |= patterns[k] <= 0x24;
-    for (size_t p = 0; low && p < npat; ++p)
-        for (uint64_t k = offsets[p]; k < offsets[p + 1]; ++k)
-            if (patterns[k] <= 0x24)
-                return fail(GX_EINVAL, "pattern " + std::to_string(p) + ": byte " + std::to_string((int)patterns[k]) +
-                                           " at offset " + std::to_string(k - offsets[p]) + " is not above '$'");
     if (npat == 0) {
         if (hit_offsets) hit_offsets[0] = 0;
         return GX_OK;
@@ -333,5 +592,53 @@ extern "C" int gx_search_info(const gx_context* ctx, uint64_t* word_compares, do
     if (word_compares) *word_compares = ctx->srch_words;
     if (search_ms) *search_ms = ctx->srch_ms;
     if (locate_ms) *locate_ms = ctx->srch_locate_ms;
+    return GX_OK;
+}
+
+extern "C" int gx_suffix_index_search_approx(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets,
+                                             size_t npat, uint32_t k, gx_approx_hit* hits, uint32_t max_hits,
+                                             uint32_t* positions, uint8_t* distances, size_t positions_cap,
+                                             uint64_t* hit_offsets) {
+    if (!idx) return fail(GX_EINVAL, "idx is NULL");
+    if (!offsets) return fail(GX_EINVAL, "offsets is NULL");
+    if (npat && !hits) return fail(GX_EINVAL, "hits is NULL");
+    if (positions && !hit_offsets) return fail(GX_EINVAL, "hit_offsets is NULL with positions");
+    if (positions && !distances) return fail(GX_EINVAL, "distances is NULL with positions");
+    if (k > kAprxMaxK) return fail(GX_EINVAL, "k is " + std::to_string(k) + ", more than GX_APPROX_MAX_K = 8");
+    const int brc = check_batch(patterns, offsets, npat);
+    if (brc != GX_OK) return brc;
+    for (size_t p = 0; p < npat; ++p)
+        if (offsets[p + 1] - offsets[p] < (uint64_t)k + 1)
+            return fail(GX_EINVAL, "pattern " + std::to_string(p) + " has " + std::to_string(offsets[p + 1] - offsets[p]) +
+                                       " bytes, fewer than k + 1 = " + std::to_string(k + 1) +
+                                       ": a piece would be empty and every window would match");
+    // (the pieces are the interval kernel's patterns: their count plus one, and the scan's tile rounding, in 32 bits)
+    const uint64_t npieces = (uint64_t)npat * (k + 1);
+    if (npieces + 1 + kSufTile >= (1ull << 32))
+        return fail(GX_ERANGE, "approximate search: " + std::to_string(npieces) +
+                                   " pieces (npat * (k + 1)), 2^32 or more with the scan's rounding: split the batch");
+    const uint64_t total_bytes = offsets[npat];
+    if (npat == 0) {
+        if (hit_offsets) hit_offsets[0] = 0;
+        return GX_OK;
+    }
+    std::vector<uint32_t> offs(npat + 1);
+    for (size_t p = 0; p <= npat; ++p) offs[p] = (uint32_t)offsets[p];
+    if (idx->ctx)
+        return approx_device(idx, patterns, (size_t)total_bytes, offs.data(), (uint32_t)npat, k, hits, max_hits, positions,
+                             distances, positions_cap, hit_offsets);
+    std::vector<uint8_t> padded(total_bytes + kSufPad, 0);
+    memcpy(padded.data(), patterns, total_bytes);
+    return approx_host(idx, padded.data(), offs.data(), npat, k, hits, max_hits, positions, distances, positions_cap,
+                       hit_offsets);
+}
+
+extern "C" int gx_approx_info(const gx_context* ctx, uint64_t* candidates, uint64_t* word_compares, double* seed_ms,
+                              double* verify_ms) {
+    if (!ctx) return fail(GX_EINVAL, "ctx is NULL");
+    if (candidates) *candidates = ctx->aprx_cands;
+    if (word_compares) *word_compares = ctx->aprx_words;
+    if (seed_ms) *seed_ms = ctx->aprx_seed_ms;
+    if (verify_ms) *verify_ms = ctx->aprx_verify_ms;
     return GX_OK;
 }

@@ -97,7 +97,7 @@ EXPORTED = ["gx_last_error", "gx_version", "gx_context_create", "gx_context_dest
             "gx_common_substring_candidates_host",
             "gx_suffix_tree_stats", "gx_suffix_info", "gx_suffix_digit_passes", "gx_suffix_tile", "gx_format_suffix_stats",
             "gx_suffix_index_build", "gx_suffix_index_free", "gx_suffix_index_info", "gx_suffix_index_export",
-            "gx_suffix_index_search", "gx_search_info"]
+            "gx_suffix_index_search", "gx_search_info", "gx_suffix_index_search_approx", "gx_approx_info"]
 
 _lib = None
 
@@ -194,6 +194,8 @@ def lib():
     L.gx_suffix_index_export.argtypes = [vp, vp]
     L.gx_suffix_index_search.argtypes = [vp, vp, vp, sz, vp, ctypes.c_uint32, vp, sz, vp]
     L.gx_search_info.argtypes = [vp, u64p, dp, dp]
+    L.gx_suffix_index_search_approx.argtypes = [vp, vp, vp, sz, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, sz, vp]
+    L.gx_approx_info.argtypes = [vp, u64p, u64p, dp, dp]
     _lib = L
     return L
 
@@ -1045,6 +1047,9 @@ def suffix_tile() -> Tuple[int, int, int]:
 # search mode (no counterpart in the reference)
 
 HIT_DTYPE = np.dtype([("lo", "<u4"), ("count", "<u4"), ("prefix_len", "<u4"), ("prefix_pos", "<u4")])
+APPROX_HIT_DTYPE = np.dtype([("count", "<u4"), ("best_dist", "<u4"), ("best_pos", "<u4"), ("candidates", "<u4")])
+APPROX_MAX_K = 8        # GX_APPROX_MAX_K
+NO_DIST = 0xFFFFFFFF    # best_dist of a pattern without an occurrence
 ALL_HITS = 0xFFFFFFFF   # max_hits: every occurrence
 _FIRST_CAP = 1 << 22    # positions asked for before the count is known (GX_ECAP names the rest)
 
@@ -1063,12 +1068,9 @@ class SuffixIndex:
         self.ptr = p
         self.n = len(seq)
 
-    def search(self, patterns, max_hits: int = 0) -> dict:
-        """gx_suffix_index_search for a batch: `patterns` is a sequence of bytes, or (packed, offsets) with
-        pattern p = packed[offsets[p]:offsets[p + 1]].  Returns uint32 arrays "lo", "count", "prefix_len",
-        "prefix_pos" (one entry per pattern) and, with max_hits > 0, "positions" (the first
-        min(count, max_hits) suffix-array entries of each pattern's interval, ascending) and "hit_offsets"
-        (uint64, npat + 1).  max_hits = ALL_HITS reports every occurrence."""
+    @staticmethod
+    def _batch(patterns):
+        """(packed uint8, offsets uint64, npat) of a sequence of bytes or a (packed, offsets) pair."""
         if isinstance(patterns, tuple):
             packed, off = patterns
             packed = np.ascontiguousarray(np.frombuffer(packed, np.uint8) if isinstance(packed, (bytes, bytearray))
@@ -1078,9 +1080,17 @@ class SuffixIndex:
             packed = np.frombuffer(b"".join(patterns), np.uint8)
             off = np.zeros(len(patterns) + 1, np.uint64)
             np.cumsum(np.fromiter((len(x) for x in patterns), np.uint64, len(patterns)), out=off[1:])
-        npat = len(off) - 1
         if packed.size == 0:
             packed = np.zeros(1, np.uint8)
+        return packed, off, len(off) - 1
+
+    def search(self, patterns, max_hits: int = 0) -> dict:
+        """gx_suffix_index_search for a batch: `patterns` is a sequence of bytes, or (packed, offsets) with
+        pattern p = packed[offsets[p]:offsets[p + 1]].  Returns uint32 arrays "lo", "count", "prefix_len",
+        "prefix_pos" (one entry per pattern) and, with max_hits > 0, "positions" (the first
+        min(count, max_hits) suffix-array entries of each pattern's interval, ascending) and "hit_offsets"
+        (uint64, npat + 1).  max_hits = ALL_HITS reports every occurrence."""
+        packed, off, npat = self._batch(patterns)
         hits = np.zeros(npat, HIT_DTYPE)
         out = None
         if max_hits <= 0:
@@ -1099,6 +1109,36 @@ class SuffixIndex:
             _check(rc)
             out = {"positions": pos[:int(hoff[-1])], "hit_offsets": hoff}
         r = {k: np.ascontiguousarray(hits[k]) for k in ("lo", "count", "prefix_len", "prefix_pos")}
+        if out:
+            r.update(out)
+        return r
+
+    def search_approx(self, patterns, k: int, max_hits: int = 0) -> dict:
+        """gx_suffix_index_search_approx for a batch (`patterns` as for search): every start where a pattern
+        matches with at most k substitutions (0 <= k <= APPROX_MAX_K, every pattern of k + 1 bytes or more).
+        Returns uint32 arrays "count", "best_dist" (NO_DIST without an occurrence), "best_pos", "candidates"
+        and, with max_hits > 0, "positions" (ascending per pattern), "distances" (uint8, beside them) and
+        "hit_offsets" (uint64, npat + 1).  max_hits = ALL_HITS reports every occurrence."""
+        packed, off, npat = self._batch(patterns)
+        hits = np.zeros(npat, APPROX_HIT_DTYPE)
+        out = None
+        if max_hits <= 0:
+            _check(lib().gx_suffix_index_search_approx(self.ptr, packed.ctypes.data, off.ctypes.data, npat, k,
+                                                       hits.ctypes.data, 0, None, None, 0, None))
+        else:
+            hoff = np.zeros(npat + 1, np.uint64)
+            cap = max(1, min(npat * min(max_hits, self.n + 1), _FIRST_CAP))
+            for _ in range(2):
+                pos, dst = np.zeros(cap, np.uint32), np.zeros(cap, np.uint8)
+                rc = lib().gx_suffix_index_search_approx(self.ptr, packed.ctypes.data, off.ctypes.data, npat, k,
+                                                         hits.ctypes.data, max_hits, pos.ctypes.data, dst.ctypes.data,
+                                                         cap, hoff.ctypes.data)
+                if rc != 7:
+                    break
+                cap = int(hoff[-1])   # GX_ECAP: hit_offsets is complete; allocate and repeat
+            _check(rc)
+            out = {"positions": pos[:int(hoff[-1])], "distances": dst[:int(hoff[-1])], "hit_offsets": hoff}
+        r = {f: np.ascontiguousarray(hits[f]) for f in ("count", "best_dist", "best_pos", "candidates")}
         if out:
             r.update(out)
         return r
@@ -1135,6 +1175,16 @@ def search_info(ctx: Optional["Context"] = None) -> dict:
     ms = [ctypes.c_double() for _ in range(2)]
     _check(lib().gx_search_info(ctx.ptr, ctypes.byref(w), *[ctypes.byref(x) for x in ms]))
     return {"word_compares": w.value, "search_ms": ms[0].value, "locate_ms": ms[1].value}
+
+
+def approx_info(ctx: Optional["Context"] = None) -> dict:
+    """gx_approx_info of the last approximate search on ctx: seed hits, 8-byte steps of the verify kernel,
+    device ms of the seed stages and of verify and compact."""
+    ctx = ctx or default_context()
+    c, w = ctypes.c_uint64(), ctypes.c_uint64()
+    ms = [ctypes.c_double() for _ in range(2)]
+    _check(lib().gx_approx_info(ctx.ptr, ctypes.byref(c), ctypes.byref(w), *[ctypes.byref(x) for x in ms]))
+    return {"candidates": c.value, "word_compares": w.value, "seed_ms": ms[0].value, "verify_ms": ms[1].value}
 
 
 # STRING_TERMINATORS (tree.rs:66-69)

@@ -519,6 +519,48 @@ int  gx_suffix_index_search(gx_suffix_index* idx, const uint8_t* patterns, const
  * counts only).  Measurement and tests. */
 int  gx_search_info(const gx_context* ctx, uint64_t* word_compares, double* search_ms, double* locate_ms);
 
+/* ---- approximate search: at most k substitutions -------------
+ * Conventions as above; one k for the whole call, 0 <= k <= GX_APPROX_MAX_K,
+ * and every pattern has m >= k + 1 bytes.  An occurrence of P is a start i
+ * with 0 <= i and i + m <= n (the window never touches '$') and
+ * d(i) = |{ j : s[i + j] != P[j] }| <= k.  Substitutions only: no indels.
+ *   count       the number of occurrences, overlapping ones included; max_hits
+ *               does not reduce it
+ *   best_dist   the smallest d(i) over them, 0xFFFFFFFF when count = 0
+ *   best_pos    the smallest i with d(i) = best_dist, 0 when count = 0
+ *   candidates  the seed hits verified for this pattern (the work measure)
+ * P is cut into k + 1 pieces, piece j = [floor(j m / (k + 1)), floor((j + 1) m
+ * / (k + 1))); an occurrence leaves at least one piece intact, so it is among
+ * the exact hits of the pieces (the seeds), shifted by the piece's start; the
+ * first intact piece alone reports it. */
+#define GX_APPROX_MAX_K 8
+typedef struct gx_approx_hit { uint32_t count, best_dist, best_pos, candidates; } gx_approx_hit;
+
+/* hits[p] as above.  With positions, pattern p reports q_p = min(count_p,
+ * max_hits) occurrences at positions[hit_offsets[p] .. hit_offsets[p + 1]),
+ * ascending, with their distances beside them in distances[].  When count_p >
+ * max_hits they are the first max_hits in candidate order (piece index, then
+ * suffix-array order within the piece's interval), then sorted; the host index
+ * and the device keep the same ones.  Errors as gx_suffix_index_search, and
+ * GX_EINVAL: k > GX_APPROX_MAX_K, a pattern shorter than k + 1 bytes (named),
+ * distances NULL with positions.  GX_ERANGE: npat (k + 1) + 1 at or above
+ * 2^32; the seed hits of the batch come to more than GX_APPROX_CAND_BUDGET
+ * (environment, read on every call; default 2^27, at most 2^31; about 12 pooled
+ * device bytes a candidate): nothing is verified and of hits[] only the
+ * candidates fields are written; split the batch, lower k or raise the budget.
+ * GX_ECAP: hits[] and hit_offsets[] are complete, positions[] and distances[]
+ * are untouched. */
+int  gx_suffix_index_search_approx(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets /* npat+1 */,
+                                   size_t npat, uint32_t k, gx_approx_hit* hits /* npat */, uint32_t max_hits,
+                                   uint32_t* positions /* may be NULL: counts only */,
+                                   uint8_t* distances /* may be NULL iff positions is NULL */, size_t positions_cap,
+                                   uint64_t* hit_offsets /* npat+1, may be NULL iff positions is NULL */);
+/* The last approximate search on ctx: the seed hits of the batch, the 8-byte
+ * steps of the verify kernel, device time (ms) of pieces, seeds, total and
+ * candidate offsets, and of verify and compact.  Measurement and tests. */
+int  gx_approx_info(const gx_context* ctx, uint64_t* candidates, uint64_t* word_compares, double* seed_ms,
+                    double* verify_ms);
+
 #ifdef __cplusplus
 }
 #endif
