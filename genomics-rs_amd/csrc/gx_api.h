@@ -341,6 +341,9 @@ struct gx_context {
     // the last approximate search (gx_approx_info; gx_api_search.cpp)
     uint64_t aprx_cands = 0, aprx_words = 0;
     double aprx_seed_ms = 0.0, aprx_verify_ms = 0.0;
+    // the last edit search (gx_edit_info; gx_api_search.cpp)
+    uint64_t edit_cands = 0, edit_ends = 0, edit_cells = 0;
+    double edit_seed_ms = 0.0, edit_verify_ms = 0.0, edit_dedupe_ms = 0.0;
 };
 
 struct PairHost {

@@ -17,8 +17,13 @@
 //                  exact search (the seeds), the seed hits summed in 64 bits and
 //                  held against GX_APPROX_CAND_BUDGET, then the verify walk of
 //                  gx_approx.h on every seed hit.  Device: gx_approx.hip
+//   edit           k differences, both sides: the same seeds, the
+//                  band of gx_edit.h on every seed hit, the reported ends sorted
+//                  and each run's minimum kept, then the starts of the reported
+//                  occurrences.  Device: gx_edit.hip
 #include "gx_api.h"
 #include "gx_approx.h"
+#include "gx_edit.h"
 #include "gx_search.h"
 
 struct gx_suffix_index {
@@ -463,6 +468,303 @@ int approx_device(gx_suffix_index* idx, const uint8_t* pats, size_t total_bytes,
     return GX_OK;
 }
 
+// ---------------------------------------------------------------------------
+// k differences: the same seeds, then the band of gx_edit.h on
+// every seed hit, the reported (pattern, end, distance) triples sorted and the
+// minimum taken over every run of equal ends, host and device alike
+
+static_assert(sizeof(gx_edit_hit) == sizeof(EditHit), "gx_edit_hit layout");
+static_assert(GX_EDIT_MAX_M == kEditMaxM, "GX_EDIT_MAX_M");
+
+int edit_seed_error(uint64_t total, uint64_t budget) {
+    return fail(GX_ERANGE, "edit search: " + std::to_string(total) + " seed hits, more than GX_APPROX_CAND_BUDGET = " +
+                               std::to_string(budget) + ": split the batch, lower k, or raise GX_APPROX_CAND_BUDGET");
+}
+
+int edit_ends_error(uint64_t total, uint64_t budget) {
+    return fail(GX_ERANGE, "edit search: " + std::to_string(total) +
+                               " reported ends before dedupe, more than GX_APPROX_CAND_BUDGET = " + std::to_string(budget) +
+                               ": split the batch, lower k, or raise GX_APPROX_CAND_BUDGET");
+}
+
+void edit_candidates_only(const SrchHit* ph, size_t npat, uint32_t k1, gx_edit_hit* hits) {
+    for (size_t p = 0; p < npat; ++p) {
+        uint64_t c = 0;
+        for (uint32_t j = 0; j < k1; ++j) c += ph[p * k1 + j].count;
+        hits[p].candidates = (uint32_t)std::min<uint64_t>(c, 0xFFFFFFFFull);
+    }
+}
+
+// The radix passes that sort pattern << 32 | end: a key byte that is zero in
+// every key (ends <= n, patterns < npat) is skipped, as the suffix sort's masks
+// skip constant digits.
+bool edit_pass_needed(int p, uint32_t n, uint32_t npat) {
+    return p < 4 ? (n >> (8 * p)) != 0 : ((npat - 1) >> (8 * (p - 4))) != 0;
+}
+
+// pats: padded as for search_host.
+int edit_host(const gx_suffix_index* idx, const uint8_t* pats, const uint32_t* offs, size_t npat, uint32_t k,
+              gx_edit_hit* hits, uint32_t max_hits, uint32_t* ends, uint8_t* distances, uint32_t* starts, size_t cap,
+              uint64_t* hit_offsets) {
+    const uint32_t n = (uint32_t)idx->n, N = n + 1, k1 = k + 1;
+    const uint8_t* t = idx->text.data();
+    const uint32_t* sa = idx->sa.data();
+    std::vector<SrchHit> ph(npat * k1);
+    uint64_t words = 0, total = 0, cells = 0;
+    for (size_t p = 0; p < npat; ++p) {
+        const uint32_t m = offs[p + 1] - offs[p];
+        for (uint32_t j = 0; j < k1; ++j) {
+            const uint32_t ps = aprx_piece_start(m, k1, j), pe = aprx_piece_start(m, k1, j + 1);
+            ph[p * k1 + j] = srch_one(t, sa, N, pats + offs[p] + ps, pe - ps, &words);
+            total += ph[p * k1 + j].count;
+        }
+    }
+    const uint64_t budget = approx_budget();
+    if (total > budget) {
+        edit_candidates_only(ph.data(), npat, k1, hits);
+        return edit_seed_error(total, budget);
+    }
+    // verify: every reported (pattern << 32 | end, distance), in candidate order
+    std::vector<std::pair<uint64_t, uint32_t>> rep;
+    for (size_t p = 0; p < npat; ++p) {
+        const uint32_t m = offs[p + 1] - offs[p];
+        for (uint32_t j = 0; j < k1; ++j) {
+            const SrchHit& s = ph[p * k1 + j];
+            const uint32_t ps = aprx_piece_start(m, k1, j);
+            for (uint32_t r = 0; r < s.count; ++r) {
+                const int64_t d0 = (int64_t)sa[s.lo + r] - (int64_t)ps;
+                if (!edit_diag_ok(d0, n, m, k)) continue;
+                uint32_t mk = 0;
+                uint64_t nb = 0;
+                if (!edit_band_host(t, n, pats + offs[p], m, k, (int32_t)d0, &mk, &nb, &cells)) continue;
+                for (uint32_t sl = 0; sl < 2 * k + 1; ++sl)
+                    if ((mk >> sl) & 1u)
+                        rep.emplace_back((uint64_t)p << 32 | (uint32_t)((int64_t)m + d0 - k + sl), edit_slot_dist(mk, nb, sl));
+                if (rep.size() > budget) {
+                    // (the device sums every candidate's ends before it refuses; the host stops at the first one over)
+                    edit_candidates_only(ph.data(), npat, k1, hits);
+                    return edit_ends_error(rep.size(), budget);
+                }
+            }
+        }
+    }
+    // dedupe: sorted by key, candidate order kept within a run; a head takes its run's minimum
+    std::stable_sort(rep.begin(), rep.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    const uint64_t E = rep.size();
+    std::vector<uint64_t> keys(E);
+    std::vector<uint32_t> vals(E);
+    for (uint64_t i = 0; i < E; ++i) {
+        keys[i] = rep[i].first;
+        vals[i] = rep[i].second;
+    }
+    rep = std::vector<std::pair<uint64_t, uint32_t>>();
+    std::vector<uint64_t> out;   // end << 8 | distance, the reported ones of every pattern in turn
+    const uint32_t bound = edit_run_bound(k);
+    uint64_t i = 0;
+    for (size_t p = 0; p < npat; ++p) {
+        gx_edit_hit h{0, 0xFFFFFFFFu, 0, 0};
+        for (uint32_t j = 0; j < k1; ++j) h.candidates += ph[p * k1 + j].count;
+        uint64_t best = ~0ull;
+        for (; i < E && (keys[i] >> 32) == p; ++i) {
+            if (i && keys[i - 1] == keys[i]) continue;   // not a head
+            const uint32_t d = edit_run_min(keys.data(), vals.data(), i, E, bound), e = (uint32_t)keys[i];
+            best = std::min(best, (uint64_t)d << 32 | e);
+            if (ends && h.count < max_hits) out.push_back((uint64_t)e << 8 | d);
+            ++h.count;
+        }
+        if (h.count) {
+            h.best_dist = (uint32_t)(best >> 32);
+            h.best_end = (uint32_t)best;
+        }
+        hits[p] = h;
+    }
+    if (!ends) {
+        if (hit_offsets) offsets_of(hits, npat, max_hits, hit_offsets);
+        return GX_OK;
+    }
+    const uint64_t total_out = offsets_of(hits, npat, max_hits, hit_offsets);
+    if (total_out > cap) return cap_error(total_out, cap);
+    for (size_t p = 0; p < npat; ++p)
+        for (uint64_t o = hit_offsets[p]; o < hit_offsets[p + 1]; ++o) {
+            ends[o] = (uint32_t)(out[o] >> 8);
+            distances[o] = (uint8_t)out[o];
+            if (starts)
+                starts[o] = edit_start_host(t, ends[o], pats + offs[p], offs[p + 1] - offs[p], k, distances[o], &cells);
+        }
+    return GX_OK;
+}
+
+// pats: unpadded, as for search_device.  Takes ctx->mu.
+int edit_device(gx_suffix_index* idx, const uint8_t* pats, size_t total_bytes, const uint32_t* offs, uint32_t npat,
+                uint32_t k, gx_edit_hit* hits, uint32_t max_hits, uint32_t* ends, uint8_t* distances, uint32_t* starts,
+                size_t cap, uint64_t* hit_offsets) {
+    gx_context* ctx = idx->ctx;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    hipStream_t st = ctx->stream;
+    const uint32_t n = (uint32_t)idx->n, N = n + 1, k1 = k + 1, npieces = npat * k1;
+    ctx->edit_cands = ctx->edit_ends = ctx->edit_cells = 0;
+    ctx->edit_seed_ms = ctx->edit_verify_ms = ctx->edit_dedupe_ms = 0.0;
+    DevBuf d_pat, d_off, d_poff, d_phits, d_coff, d_tmp, d_small, d_ecnt, d_etmp, d_rep, d_nib, d_key[2], d_val[2], d_table,
+        d_stmp, d_head, d_best, d_hits, d_hbase, d_oq, d_pos, d_dst, d_sta;
+    auto done = [&](int rc) {
+        if (rc != GX_OK) (void)hipStreamSynchronize(st);   // nothing of this call still runs on the buffers
+        for (DevBuf* b : {&d_pat, &d_off, &d_poff, &d_phits, &d_coff, &d_tmp, &d_small, &d_ecnt, &d_etmp, &d_rep, &d_nib,
+                          &d_key[0], &d_key[1], &d_val[0], &d_val[1], &d_table, &d_stmp, &d_head, &d_best, &d_hits,
+                          &d_hbase, &d_oq, &d_pos, &d_dst, &d_sta})
+            pool_put(ctx, *b);
+        return rc;
+    };
+#define SR_TRY(expr)                                                                                          \
+    do {                                                                                                      \
+        hipError_t e_ = (expr);                                                                               \
+        if (e_ != hipSuccess)                                                                                 \
+            return done(fail(e_ == hipErrorOutOfMemory ? GX_ENOMEM : GX_EHIP,                                 \
+                             std::string(#expr) + ": " + hipGetErrorString(e_)));                             \
+    } while (0)
+#define SR_GET(buf, bytes)                                                      \
+    do {                                                                        \
+        const int rc_ = pool_get(ctx, (bytes), &(buf), st);                     \
+        if (rc_ != GX_OK) return done(rc_);                                     \
+    } while (0)
+    SR_GET(d_pat, total_bytes + kSufPad);
+    SR_GET(d_off, ((size_t)npat + 1) * 4);
+    SR_GET(d_poff, ((size_t)npieces + 1) * 4);
+    SR_GET(d_phits, (size_t)npieces * sizeof(SrchHit));
+    SR_GET(d_coff, ((size_t)npieces + 1) * 4);
+    SR_GET(d_tmp, suf_tiles((size_t)npieces + 1) * 4);
+    SR_GET(d_small, 64);
+    unsigned long long* d_cnt = (unsigned long long*)d_small.p;   // [0] seed word steps, [1] seed hits, [2] ends before dedupe, [3] cell updates
+    SR_TRY(hipMemcpyAsync(d_pat.p, pats, total_bytes, hipMemcpyHostToDevice, st));
+    SR_TRY(hipMemsetAsync((uint8_t*)d_pat.p + total_bytes, 0, kSufPad, st));
+    SR_TRY(hipMemcpyAsync(d_off.p, offs, ((size_t)npat + 1) * 4, hipMemcpyHostToDevice, st));
+    SR_TRY(hipMemsetAsync(d_cnt, 0, 32, st));
+    const uint8_t* text = (const uint8_t*)idx->d_text.p;
+    const uint32_t* sa = (const uint32_t*)idx->d_sa.p;
+    const uint8_t* dp = (const uint8_t*)d_pat.p;
+    const uint32_t* off = (const uint32_t*)d_off.p;
+    uint32_t* poff = (uint32_t*)d_poff.p;
+    SrchHit* ph = (SrchHit*)d_phits.p;
+    uint32_t* coff = (uint32_t*)d_coff.p;
+    // pieces, seeds, their 64-bit total, candidate offsets: DESIGN.md 19.2 stages 1 to 4
+    SR_TRY(hipEventRecord(ctx->ev0, st));
+    SR_TRY(launch_aprx_pieces(off, npat, k1, poff, st));
+    SR_TRY(launch_srch_range(text, sa, N, dp, poff, npieces, ph, d_cnt, st));
+    SR_TRY(launch_aprx_total(ph, npieces, d_cnt + 1, st));
+    SR_TRY(launch_srch_clamp(ph, npieces, 0xFFFFFFFFu, coff, st));
+    SR_TRY(launch_suf_scan(coff, npieces + 1, false, (uint32_t*)d_tmp.p, st));
+    SR_TRY(hipEventRecord(ctx->ev1, st));
+    unsigned long long* pin = (unsigned long long*)io_pinned(ctx, 128);
+    if (!pin) return done(fail(GX_ENOMEM, "edit search: pinned staging"));
+    SR_TRY(hipMemcpyAsync(pin, d_cnt, 16, hipMemcpyDeviceToHost, st));
+    SR_TRY(hipStreamSynchronize(st));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) ctx->edit_seed_ms = ms;
+    const uint64_t total = pin[1], budget = approx_budget();
+    ctx->edit_cands = total;
+    std::vector<SrchHit> hp;   // the refusals' only output comes from the pieces' intervals
+    auto refuse = [&](int rc) {
+        hp.resize(npieces);
+        if (hipMemcpyAsync(hp.data(), ph, (size_t)npieces * sizeof(SrchHit), hipMemcpyDeviceToHost, st) == hipSuccess &&
+            hipStreamSynchronize(st) == hipSuccess)
+            edit_candidates_only(hp.data(), npat, k1, hits);
+        return done(rc);
+    };
+    if (total > budget) return refuse(edit_seed_error(total, budget));
+    // the band on every candidate; what it reports is summed in 64 bits and held against the budget
+    // before the 32-bit scan of the numbers is relied upon
+    const uint32_t T = (uint32_t)total;   // <= 2^31
+    SR_GET(d_ecnt, ((size_t)T + 1) * 4);
+    SR_GET(d_etmp, suf_tiles((size_t)T + 1) * 4);
+    SR_GET(d_rep, std::max<size_t>(T, 1) * 4);
+    SR_GET(d_nib, std::max<size_t>(T, 1) * 8);
+    uint32_t* ecnt = (uint32_t*)d_ecnt.p;
+    SR_TRY(hipEventRecord(ctx->ev1, st));
+    SR_TRY(launch_edit_verify(text, sa, N, dp, off, poff, ph, coff, npieces, k, T, ecnt, (uint32_t*)d_rep.p,
+                              (uint64_t*)d_nib.p, d_cnt + 2, d_cnt + 3, st));
+    SR_TRY(hipEventRecord(ctx->ev2, st));
+    SR_TRY(hipMemcpyAsync(pin + 2, d_cnt + 2, 16, hipMemcpyDeviceToHost, st));
+    SR_TRY(hipStreamSynchronize(st));
+    if (hipEventElapsedTime(&ms, ctx->ev1, ctx->ev2) == hipSuccess) ctx->edit_verify_ms = ms;
+    ctx->edit_ends = pin[2];
+    ctx->edit_cells = pin[3];
+    if (pin[2] > budget) return refuse(edit_ends_error(pin[2], budget));
+    // dedupe: scan, emit, sort, heads, scan, fill, scan, scatter; then the starts
+    const uint32_t E = (uint32_t)pin[2];   // <= 2^31
+    const size_t tiles = suf_tiles(E), table_n = 256 * tiles;
+    const uint64_t dev_cap =
+        ends ? std::min<uint64_t>(std::min<uint64_t>(cap, E), (uint64_t)npat * std::min(max_hits, N)) : 0;
+    for (int q = 0; q < 2; ++q) {
+        SR_GET(d_key[q], std::max<size_t>(E, 1) * 8);
+        SR_GET(d_val[q], std::max<size_t>(E, 1) * 4);
+    }
+    SR_GET(d_table, std::max<size_t>(table_n, 1) * 4);
+    SR_GET(d_stmp, std::max<size_t>(std::max(suf_tiles(table_n), suf_tiles((size_t)E + 1)), 1) * 4);
+    SR_GET(d_head, ((size_t)E + 1) * 4);
+    SR_GET(d_best, (size_t)npat * 8);
+    SR_GET(d_hits, (size_t)npat * sizeof(EditHit));
+    SR_GET(d_hbase, (size_t)npat * 4);
+    SR_GET(d_oq, ((size_t)npat + 1) * 4);
+    if (dev_cap) {
+        SR_GET(d_pos, (size_t)dev_cap * 4);
+        SR_GET(d_dst, (size_t)dev_cap);
+        if (starts) SR_GET(d_sta, (size_t)dev_cap * 4);
+    }
+    int cur = 0;
+    auto K = [&](int q) { return (uint64_t*)d_key[q].p; };
+    auto V = [&](int q) { return (uint32_t*)d_val[q].p; };
+    uint32_t* head = (uint32_t*)d_head.p;
+    uint32_t* oq = (uint32_t*)d_oq.p;
+    SR_TRY(hipMemsetAsync(d_best.p, 0xFF, (size_t)npat * 8, st));
+    SR_TRY(hipEventRecord(ctx->ev1, st));
+    if (E) {
+        SR_TRY(launch_suf_scan(ecnt, T + 1, false, (uint32_t*)d_etmp.p, st));
+        SR_TRY(launch_edit_emit(sa, N, off, poff, ph, coff, npieces, k, T, ecnt, (const uint32_t*)d_rep.p,
+                                (const uint64_t*)d_nib.p, K(cur), V(cur), st));
+        for (int p = 0; p < 8; ++p) {
+            if (!edit_pass_needed(p, n, npat)) continue;
+            SR_TRY(launch_suf_sort_pass(K(cur), V(cur), K(cur ^ 1), V(cur ^ 1), E, 8 * p, (uint32_t*)d_table.p,
+                                        (uint32_t*)d_stmp.p, st));
+            cur ^= 1;
+        }
+    }
+    uint32_t* dmin = V(cur ^ 1);   // (the sort's other buffer is free now)
+    SR_TRY(launch_edit_heads(K(cur), V(cur), E, k, head, dmin, (unsigned long long*)d_best.p, st));
+    SR_TRY(launch_suf_scan(head, E + 1, false, (uint32_t*)d_stmp.p, st));
+    SR_TRY(launch_edit_fill(K(cur), head, E, coff, (const unsigned long long*)d_best.p, npat, k1, max_hits,
+                            (EditHit*)d_hits.p, (uint32_t*)d_hbase.p, oq, st));
+    if (dev_cap) {
+        SR_TRY(launch_suf_scan(oq, npat + 1, false, (uint32_t*)d_tmp.p, st));
+        SR_TRY(launch_edit_scatter(K(cur), dmin, head, E, (const uint32_t*)d_hbase.p, oq, npat, max_hits,
+                                   (uint32_t*)d_pos.p, (uint8_t*)d_dst.p, dev_cap, st));
+        if (starts)
+            SR_TRY(launch_edit_starts(text, dp, off, oq, npat, k, (const uint32_t*)d_pos.p, (const uint8_t*)d_dst.p,
+                                      (uint32_t*)d_sta.p, dev_cap, st));
+    }
+    SR_TRY(hipEventRecord(ctx->ev2, st));
+    // (behind the last event: the events time kernels alone)
+    SR_TRY(hipMemcpyAsync(hits, d_hits.p, (size_t)npat * sizeof(EditHit), hipMemcpyDeviceToHost, st));
+    SR_TRY(hipStreamSynchronize(st));
+    if (hipEventElapsedTime(&ms, ctx->ev1, ctx->ev2) == hipSuccess) ctx->edit_dedupe_ms = ms;
+    if (!ends) {
+        if (hit_offsets) offsets_of(hits, npat, max_hits, hit_offsets);
+        return done(GX_OK);
+    }
+    // the occurrences: their number is known to the host only now, so that GX_ECAP leaves the three arrays
+    // untouched and the copies move no more than them (a total above dev_cap is above cap)
+    const uint64_t total_out = offsets_of(hits, npat, max_hits, hit_offsets);
+    if (total_out > cap) return done(cap_error(total_out, cap));
+    if (total_out) {
+        SR_TRY(hipMemcpyAsync(ends, d_pos.p, (size_t)total_out * 4, hipMemcpyDeviceToHost, st));
+        SR_TRY(hipMemcpyAsync(distances, d_dst.p, (size_t)total_out, hipMemcpyDeviceToHost, st));
+        if (starts) SR_TRY(hipMemcpyAsync(starts, d_sta.p, (size_t)total_out * 4, hipMemcpyDeviceToHost, st));
+        SR_TRY(hipStreamSynchronize(st));
+    }
+#undef SR_TRY
+#undef SR_GET
+    return done(GX_OK);   // (the stream is idle)
+}
+
 }  // namespace
 
 // ---------------------------------------------------------------------------
@@ -640,5 +942,60 @@ extern "C" int gx_approx_info(const gx_context* ctx, uint64_t* candidates, uint6
     if (word_compares) *word_compares = ctx->aprx_words;
     if (seed_ms) *seed_ms = ctx->aprx_seed_ms;
     if (verify_ms) *verify_ms = ctx->aprx_verify_ms;
+    return GX_OK;
+}
+
+extern "C" int gx_suffix_index_search_edit(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets,
+                                           size_t npat, uint32_t k, gx_edit_hit* hits, uint32_t max_hits, uint32_t* ends,
+                                           uint8_t* distances, uint32_t* starts, size_t positions_cap,
+                                           uint64_t* hit_offsets) {
+    if (!idx) return fail(GX_EINVAL, "idx is NULL");
+    if (!offsets) return fail(GX_EINVAL, "offsets is NULL");
+    if (npat && !hits) return fail(GX_EINVAL, "hits is NULL");
+    if (ends && !hit_offsets) return fail(GX_EINVAL, "hit_offsets is NULL with ends");
+    if (ends && !distances) return fail(GX_EINVAL, "distances is NULL with ends");
+    if (starts && !ends) return fail(GX_EINVAL, "starts without ends");
+    if (k > kAprxMaxK) return fail(GX_EINVAL, "k is " + std::to_string(k) + ", more than GX_APPROX_MAX_K = 8");
+    const int brc = check_batch(patterns, offsets, npat);
+    if (brc != GX_OK) return brc;
+    for (size_t p = 0; p < npat; ++p) {
+        const uint64_t m = offsets[p + 1] - offsets[p];
+        if (m < (uint64_t)k + 1)
+            return fail(GX_EINVAL, "pattern " + std::to_string(p) + " has " + std::to_string(m) +
+                                       " bytes, fewer than k + 1 = " + std::to_string(k + 1) +
+                                       ": a piece would be empty and every end would match");
+        if (m > kEditMaxM)
+            return fail(GX_ERANGE, "pattern " + std::to_string(p) + " has " + std::to_string(m) +
+                                       " bytes, more than GX_EDIT_MAX_M = 4096");
+    }
+    const uint64_t npieces = (uint64_t)npat * (k + 1);
+    if (npieces + 1 + kSufTile >= (1ull << 32))
+        return fail(GX_ERANGE, "edit search: " + std::to_string(npieces) +
+                                   " pieces (npat * (k + 1)), 2^32 or more with the scan's rounding: split the batch");
+    const uint64_t total_bytes = offsets[npat];
+    if (npat == 0) {
+        if (hit_offsets) hit_offsets[0] = 0;
+        return GX_OK;
+    }
+    std::vector<uint32_t> offs(npat + 1);
+    for (size_t p = 0; p <= npat; ++p) offs[p] = (uint32_t)offsets[p];
+    if (idx->ctx)
+        return edit_device(idx, patterns, (size_t)total_bytes, offs.data(), (uint32_t)npat, k, hits, max_hits, ends,
+                           distances, starts, positions_cap, hit_offsets);
+    std::vector<uint8_t> padded(total_bytes + kSufPad, 0);
+    memcpy(padded.data(), patterns, total_bytes);
+    return edit_host(idx, padded.data(), offs.data(), npat, k, hits, max_hits, ends, distances, starts, positions_cap,
+                     hit_offsets);
+}
+
+extern "C" int gx_edit_info(const gx_context* ctx, uint64_t* candidates, uint64_t* pre_dedupe_ends, uint64_t* cell_updates,
+                            double* seed_ms, double* verify_ms, double* dedupe_ms) {
+    if (!ctx) return fail(GX_EINVAL, "ctx is NULL");
+    if (candidates) *candidates = ctx->edit_cands;
+    if (pre_dedupe_ends) *pre_dedupe_ends = ctx->edit_ends;
+    if (cell_updates) *cell_updates = ctx->edit_cells;
+    if (seed_ms) *seed_ms = ctx->edit_seed_ms;
+    if (verify_ms) *verify_ms = ctx->edit_verify_ms;
+    if (dedupe_ms) *dedupe_ms = ctx->edit_dedupe_ms;
     return GX_OK;
 }

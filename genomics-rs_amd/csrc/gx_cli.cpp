@@ -38,7 +38,7 @@
 //       checked as the reference's tree checks it; --suffix-links is accepted
 //       and ignored; the Graphviz block of small trees is not printed.
 //
-//   gx-align search -f genome.fasta -p patterns.fasta [--max-hits K] [-k MISMATCHES] [-o hits.tsv]
+//   gx-align search -f genome.fasta -p patterns.fasta [--max-hits K] [-k MISMATCHES | -e EDITS] [-o hits.tsv]
 //       No counterpart in the reference's main.rs: where every record of
 //       patterns.fasta occurs in the first record of genome.fasta, from a
 //       suffix index kept on the GPU (gx_suffix_index_search).
@@ -47,7 +47,11 @@
 //       positions, comma-separated.  With -k: every start where the pattern
 //       matches with at most that many substitutions
 //       (gx_suffix_index_search_approx); the line is then name,
-//       length, count, best_dist, best_pos and up to K pos:dist pairs.
+//       length, count, best_dist, best_pos and up to K pos:dist pairs.  With -e
+//       (not together with -k): every end where the pattern matches with at
+//       most that many substitutions, insertions and deletions
+//       (gx_suffix_index_search_edit); the line is then name,
+//       length, count, best_dist, best_end and up to K start-end:dist triples.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -73,7 +77,7 @@ void usage() {
             "       gx-align compare -d|--fasta-dir <DIR> [-o <TSV>]\n"
             "       gx-align suffix-tree -f|--fasta-path <FASTA> [-a|--alphabet-file <ALPHABET>] [--suffix-links] "
             "[--stats] [-o <BWT>]\n"
-            "       gx-align search -f|--fasta-path <GENOME> -p|--patterns <PATTERNS> [--max-hits <K>] [-k <MISMATCHES>] [-o <TSV>]\n");
+            "       gx-align search -f|--fasta-path <GENOME> -p|--patterns <PATTERNS> [--max-hits <K>] [-k <MISMATCHES> | -e <EDITS>] [-o <TSV>]\n");
 }
 
 struct Records {
@@ -452,9 +456,10 @@ int run_suffix_tree(const std::string& fasta, const std::string& alphabet, bool 
 
 // Search mode on GPU 0 (no counterpart in the reference): every record of the
 // pattern file against the suffix index of the genome's first record.
-// -k K: at most K substitutions (gx_suffix_index_search_approx); kmis < 0: exact.
+// -k K: at most K substitutions (gx_suffix_index_search_approx); -e K: at most K
+// differences (gx_suffix_index_search_edit); both below 0: exact.
 int run_search(const std::string& fasta, const std::string& patterns, uint32_t max_hits, const std::string& out_path,
-               int kmis) {
+               int kmis, int kedit) {
     const char* lg = getenv("GX_LOG");
     const bool info = lg && (!strcmp(lg, "info") || !strcmp(lg, "debug"));
     if (info) fprintf(stderr, "[INFO] MODE: Search\n[INFO] Loading sequences from %s and %s\n", fasta.c_str(), patterns.c_str());
@@ -476,26 +481,43 @@ int run_search(const std::string& fasta, const std::string& patterns, uint32_t m
     int rc = gx_suffix_index_build(ctx, g.seq(0), g.sl[0], &idx);
     if (rc != GX_OK) { gx_context_destroy(ctx); return fail_msg("search: index", rc); }
     const auto build_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-    std::vector<gx_search_hit> hits(kmis < 0 ? npat : 0);
+    const bool exact = kmis < 0 && kedit < 0;
+    std::vector<gx_search_hit> hits(exact ? npat : 0);
     std::vector<gx_approx_hit> ahits(kmis < 0 ? 0 : npat);
+    std::vector<gx_edit_hit> ehits(kedit < 0 ? 0 : npat);
     std::vector<uint64_t> hoff(npat + 1, 0);
     std::vector<uint32_t> pos(std::max<size_t>(1, npat * (size_t)std::min<uint64_t>(max_hits, 16)));
-    std::vector<uint8_t> dst(kmis < 0 ? 0 : pos.size());
+    std::vector<uint8_t> dst(exact ? 0 : pos.size());
+    std::vector<uint32_t> sta(kedit < 0 ? 0 : pos.size());
     t0 = std::chrono::steady_clock::now();
     for (int pass = 0; pass < 2; ++pass) {   // GX_ECAP: hit_offsets is complete; allocate and repeat
-        if (kmis < 0)
+        if (exact)
             rc = gx_suffix_index_search(idx, packed.data(), off.data(), npat, hits.data(), max_hits,
                                         max_hits ? pos.data() : nullptr, pos.size(), max_hits ? hoff.data() : nullptr);
+        else if (kedit >= 0)
+            rc = gx_suffix_index_search_edit(idx, packed.data(), off.data(), npat, (uint32_t)kedit, ehits.data(), max_hits,
+                                             max_hits ? pos.data() : nullptr, max_hits ? dst.data() : nullptr,
+                                             max_hits ? sta.data() : nullptr, pos.size(), max_hits ? hoff.data() : nullptr);
         else
             rc = gx_suffix_index_search_approx(idx, packed.data(), off.data(), npat, (uint32_t)kmis, ahits.data(), max_hits,
                                                max_hits ? pos.data() : nullptr, max_hits ? dst.data() : nullptr, pos.size(),
                                                max_hits ? hoff.data() : nullptr);
         if (rc != GX_ECAP) break;
         pos.assign((size_t)hoff[npat], 0);
-        if (kmis >= 0) dst.assign((size_t)hoff[npat], 0);
+        if (!exact) dst.assign((size_t)hoff[npat], 0);
+        if (kedit >= 0) sta.assign((size_t)hoff[npat], 0);
     }
     const auto us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-    if (rc == GX_OK && info && kmis >= 0) {
+    if (rc == GX_OK && info && kedit >= 0) {
+        uint64_t cands = 0, pre = 0, cells = 0;
+        double sms = 0, vms = 0, dms = 0;
+        gx_edit_info(ctx, &cands, &pre, &cells, &sms, &vms, &dms);
+        fprintf(stderr, "[INFO] index of %llu bases built in %lld us; %zu patterns searched with at most %d differences in "
+                        "%lld us (%llu candidates, %llu ends before dedupe, %llu cell updates, seeds %.3f ms, verify %.3f ms, "
+                        "dedupe %.3f ms)\n",
+                (unsigned long long)g.sl[0], (long long)build_us, npat, kedit, (long long)us, (unsigned long long)cands,
+                (unsigned long long)pre, (unsigned long long)cells, sms, vms, dms);
+    } else if (rc == GX_OK && info && kmis >= 0) {
         uint64_t cands = 0, words = 0;
         double sms = 0, vms = 0;
         gx_approx_info(ctx, &cands, &words, &sms, &vms);
@@ -517,7 +539,12 @@ int run_search(const std::string& fasta, const std::string& patterns, uint32_t m
     FILE* f = out_path.empty() ? stdout : fopen(out_path.c_str(), "w");
     if (!f) { fprintf(stderr, "[ERROR] cannot write %s\n", out_path.c_str()); return 1; }
     for (size_t p = 0; p < npat; ++p) {
-        if (kmis < 0) {
+        if (kedit >= 0) {   // name, length, count, best_dist, best_end, start-end:dist triples
+            fprintf(f, "%s\t%llu\t%u\t%u\t%u\t", q.name(p).c_str(), (unsigned long long)q.sl[p], ehits[p].count,
+                    ehits[p].best_dist, ehits[p].best_end);
+            for (uint64_t k = hoff[p]; k < hoff[p + 1]; ++k)
+                fprintf(f, k == hoff[p] ? "%u-%u:%u" : ",%u-%u:%u", sta[k], pos[k], (unsigned)dst[k]);
+        } else if (exact) {
             fprintf(f, "%s\t%llu\t%u\t%u\t%u\t", q.name(p).c_str(), (unsigned long long)q.sl[p], hits[p].count,
                     hits[p].prefix_len, hits[p].prefix_pos);
             for (uint64_t k = hoff[p]; k < hoff[p + 1]; ++k) fprintf(f, k == hoff[p] ? "%u" : ",%u", pos[k]);
@@ -540,7 +567,7 @@ int main(int argc, char** argv) {
     setenv("GX_LOG", getenv("GX_LOG") ? getenv("GX_LOG") : "info", 1);
     std::string config = "config.toml", type, fasta, dir, tsv = "similarity_matrix.tsv", mode, patterns;
     int ngpu = 0;
-    long long max_hits = 16, kmis = -1;
+    long long max_hits = 16, kmis = -1, kedit = -1;
     bool with_self = true, stats = false, out_set = false;
     for (int k = 1; k < argc; ++k) {
         std::string a = argv[k];
@@ -558,6 +585,7 @@ int main(int argc, char** argv) {
         else if (a == "-p" || a == "--patterns") next(patterns);
         else if (a == "--max-hits") { std::string v; next(v); max_hits = atoll(v.c_str()); }
         else if (a == "-k" || a == "--mismatches") { std::string v; next(v); kmis = atoll(v.c_str()); if (kmis < 0) { usage(); return 2; } }
+        else if (a == "-e" || a == "--edits") { std::string v; next(v); kedit = atoll(v.c_str()); if (kedit < 0) { usage(); return 2; } }
         else if (a == "--suffix-links") {}   // (the reference's build strategy: no counterpart)
         else if (a == "-g" || a == "--gpus") { std::string v; next(v); ngpu = atoi(v.c_str()); }
         else if (a == "--no-self") with_self = false;
@@ -566,12 +594,13 @@ int main(int argc, char** argv) {
     }
     const bool by_file = mode == "align" || mode == "suffix-tree" || mode == "search";
     if (mode.empty() || (by_file && fasta.empty()) || (!by_file && dir.empty()) ||
-        (mode == "search" && (patterns.empty() || max_hits < 0 || max_hits > 0xFFFFFFFFll || kmis > 0xFFFF))) {
+        (mode == "search" && (patterns.empty() || max_hits < 0 || max_hits > 0xFFFFFFFFll || kmis > 0xFFFF || kedit > 0xFFFF ||
+                              (kmis >= 0 && kedit >= 0)))) {
         usage();
         return 2;
     }
     if (mode == "compare") return run_compare(dir, tsv);   // (reads no scores: main.rs:216-221)
-    if (mode == "search") return run_search(fasta, patterns, (uint32_t)max_hits, out_set ? tsv : std::string(), (int)kmis);
+    if (mode == "search") return run_search(fasta, patterns, (uint32_t)max_hits, out_set ? tsv : std::string(), (int)kmis, (int)kedit);
     if (mode == "suffix-tree") return run_suffix_tree(fasta, type, stats, out_set ? tsv : std::string());
     gx_scores sc;
     if (gx_config_load(config.c_str(), &sc) != GX_OK) {

@@ -97,7 +97,8 @@ EXPORTED = ["gx_last_error", "gx_version", "gx_context_create", "gx_context_dest
             "gx_common_substring_candidates_host",
             "gx_suffix_tree_stats", "gx_suffix_info", "gx_suffix_digit_passes", "gx_suffix_tile", "gx_format_suffix_stats",
             "gx_suffix_index_build", "gx_suffix_index_free", "gx_suffix_index_info", "gx_suffix_index_export",
-            "gx_suffix_index_search", "gx_search_info", "gx_suffix_index_search_approx", "gx_approx_info"]
+            "gx_suffix_index_search", "gx_search_info", "gx_suffix_index_search_approx", "gx_approx_info",
+            "gx_suffix_index_search_edit", "gx_edit_info"]
 
 _lib = None
 
@@ -196,6 +197,8 @@ def lib():
     L.gx_search_info.argtypes = [vp, u64p, dp, dp]
     L.gx_suffix_index_search_approx.argtypes = [vp, vp, vp, sz, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, sz, vp]
     L.gx_approx_info.argtypes = [vp, u64p, u64p, dp, dp]
+    L.gx_suffix_index_search_edit.argtypes = [vp, vp, vp, sz, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp, sz, vp]
+    L.gx_edit_info.argtypes = [vp, u64p, u64p, u64p, dp, dp, dp]
     _lib = L
     return L
 
@@ -1048,7 +1051,9 @@ def suffix_tile() -> Tuple[int, int, int]:
 
 HIT_DTYPE = np.dtype([("lo", "<u4"), ("count", "<u4"), ("prefix_len", "<u4"), ("prefix_pos", "<u4")])
 APPROX_HIT_DTYPE = np.dtype([("count", "<u4"), ("best_dist", "<u4"), ("best_pos", "<u4"), ("candidates", "<u4")])
+EDIT_HIT_DTYPE = np.dtype([("count", "<u4"), ("best_dist", "<u4"), ("best_end", "<u4"), ("candidates", "<u4")])
 APPROX_MAX_K = 8        # GX_APPROX_MAX_K
+EDIT_MAX_M = 4096       # GX_EDIT_MAX_M
 NO_DIST = 0xFFFFFFFF    # best_dist of a pattern without an occurrence
 ALL_HITS = 0xFFFFFFFF   # max_hits: every occurrence
 _FIRST_CAP = 1 << 22    # positions asked for before the count is known (GX_ECAP names the rest)
@@ -1143,6 +1148,40 @@ class SuffixIndex:
             r.update(out)
         return r
 
+    def search_edit(self, patterns, k: int, max_hits: int = 0, starts: bool = True) -> dict:
+        """gx_suffix_index_search_edit for a batch (`patterns` as for search): every end e where a pattern
+        matches a window s[b:e] with at most k substitutions, insertions and deletions (0 <= k <= APPROX_MAX_K,
+        every pattern of k + 1 to EDIT_MAX_M bytes).  Returns uint32 arrays "count", "best_dist" (NO_DIST
+        without an occurrence), "best_end", "candidates" and, with max_hits > 0, "ends" (each pattern's
+        smallest ends, ascending), "distances" (uint8), "starts" (the shortest window's; None with
+        starts=False) and "hit_offsets" (uint64, npat + 1).  max_hits = ALL_HITS reports every occurrence."""
+        packed, off, npat = self._batch(patterns)
+        hits = np.zeros(npat, EDIT_HIT_DTYPE)
+        out = None
+        if max_hits <= 0:
+            _check(lib().gx_suffix_index_search_edit(self.ptr, packed.ctypes.data, off.ctypes.data, npat, k,
+                                                     hits.ctypes.data, 0, None, None, None, 0, None))
+        else:
+            hoff = np.zeros(npat + 1, np.uint64)
+            cap = max(1, min(npat * min(max_hits, self.n + 1), _FIRST_CAP))
+            for _ in range(2):
+                end, dst = np.zeros(cap, np.uint32), np.zeros(cap, np.uint8)
+                sta = np.zeros(cap, np.uint32) if starts else None
+                rc = lib().gx_suffix_index_search_edit(self.ptr, packed.ctypes.data, off.ctypes.data, npat, k,
+                                                       hits.ctypes.data, max_hits, end.ctypes.data, dst.ctypes.data,
+                                                       sta.ctypes.data if starts else None, cap, hoff.ctypes.data)
+                if rc != 7:
+                    break
+                cap = int(hoff[-1])   # GX_ECAP: hit_offsets is complete; allocate and repeat
+            _check(rc)
+            tot = int(hoff[-1])
+            out = {"ends": end[:tot], "distances": dst[:tot], "starts": sta[:tot] if starts else None,
+                   "hit_offsets": hoff}
+        r = {f: np.ascontiguousarray(hits[f]) for f in ("count", "best_dist", "best_end", "candidates")}
+        if out:
+            r.update(out)
+        return r
+
     def sa(self) -> np.ndarray:
         """The suffix array, n + 1 entries (gx_suffix_index_export)."""
         a = np.zeros(self.n + 1, np.uint32)
@@ -1185,6 +1224,17 @@ def approx_info(ctx: Optional["Context"] = None) -> dict:
     ms = [ctypes.c_double() for _ in range(2)]
     _check(lib().gx_approx_info(ctx.ptr, ctypes.byref(c), ctypes.byref(w), *[ctypes.byref(x) for x in ms]))
     return {"candidates": c.value, "word_compares": w.value, "seed_ms": ms[0].value, "verify_ms": ms[1].value}
+
+
+def edit_info(ctx: Optional["Context"] = None) -> dict:
+    """gx_edit_info of the last edit search on ctx: seed hits, the ends they reported before equal ends were
+    merged, cell updates of the verify kernel, device ms of the seed stages, of verify and of the dedupe."""
+    ctx = ctx or default_context()
+    v = [ctypes.c_uint64() for _ in range(3)]
+    ms = [ctypes.c_double() for _ in range(3)]
+    _check(lib().gx_edit_info(ctx.ptr, *[ctypes.byref(x) for x in v + ms]))
+    return {"candidates": v[0].value, "pre_dedupe_ends": v[1].value, "cell_updates": v[2].value,
+            "seed_ms": ms[0].value, "verify_ms": ms[1].value, "dedupe_ms": ms[2].value}
 
 
 # STRING_TERMINATORS (tree.rs:66-69)

@@ -561,6 +561,52 @@ int  gx_suffix_index_search_approx(gx_suffix_index* idx, const uint8_t* patterns
 int  gx_approx_info(const gx_context* ctx, uint64_t* candidates, uint64_t* word_compares, double* seed_ms,
                     double* verify_ms);
 
+/* ---- edit search: at most k differences ----------------------
+ * Conventions as above (one k, 0 <= k <= GX_APPROX_MAX_K, every pattern of
+ * k + 1 bytes or more), and m <= GX_EDIT_MAX_M: one lane's work in one launch
+ * stays at or below m (2k + 1), about 70,000 cell updates.  ed is the
+ * unit-cost Levenshtein distance: a substitution, an insertion and a deletion
+ * cost 1 each.  For an end 0 <= e <= n,
+ *   E(e) = min over 0 <= b <= e of ed(P, s[b .. e))            (Sellers)
+ * An occurrence of P is an end e with E(e) <= k, reported as that exclusive
+ * end; its start is b(e) = max{ b : ed(P, s[b .. e)) = E(e) }, the shortest
+ * window, with e - b(e) in [m - k, m + k].  A window never contains '$'.
+ *   count       the number of ends with E(e) <= k; max_hits does not reduce it
+ *   best_dist   the smallest E(e), 0xFFFFFFFF when count = 0
+ *   best_end    the smallest e with E(e) = best_dist, 0 when count = 0
+ *   candidates  the seed hits verified for this pattern (the work measure)
+ * At k = 0 an occurrence is pos + m for each exact position pos, its start pos.
+ * The seeds are the k-mismatch search's: k edits leave one of k + 1 pieces
+ * intact.  Each seed hit is verified on the 2k + 1 diagonals around its own;
+ * E(e) is the minimum over the seed hits that report e. */
+#define GX_EDIT_MAX_M 4096
+typedef struct gx_edit_hit { uint32_t count, best_dist, best_end, candidates; } gx_edit_hit;
+
+/* hits[p] as above.  With ends, pattern p reports q_p = min(count_p, max_hits)
+ * occurrences, its q_p smallest ends, ascending, at [hit_offsets[p],
+ * hit_offsets[p + 1]) of ends[], distances[] (E(e)) and, unless it is NULL,
+ * starts[] (b(e)).  Errors as gx_suffix_index_search_approx (GX_EINVAL also for
+ * starts without ends), and GX_ERANGE: a pattern longer than GX_EDIT_MAX_M
+ * (named); the seed hits of the batch, or the ends its seed hits report before
+ * equal ends are merged (at most 2k + 1 a seed hit), come to more than
+ * GX_APPROX_CAND_BUDGET (about 16 pooled device bytes a seed hit and 29 an
+ * unmerged end): nothing further runs and of hits[] only the candidates fields
+ * are written.  GX_ECAP: hits[] and hit_offsets[] are complete, ends[],
+ * distances[] and starts[] are untouched. */
+int  gx_suffix_index_search_edit(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets /* npat+1 */,
+                                 size_t npat, uint32_t k, gx_edit_hit* hits /* npat */, uint32_t max_hits,
+                                 uint32_t* ends /* may be NULL: counts only */,
+                                 uint8_t* distances /* may be NULL iff ends is NULL */,
+                                 uint32_t* starts /* may be NULL: no start is computed */, size_t positions_cap,
+                                 uint64_t* hit_offsets /* npat+1, may be NULL iff ends is NULL */);
+/* The last edit search on ctx: the seed hits of the batch, the ends they
+ * reported before equal ends were merged, the cell updates of the verify kernel
+ * (at most sum_p candidates_p m_p (2k + 1)), and device time (ms) of the seed
+ * stages, of the verify kernel, and of scan, emit, sort, merge, scatter and
+ * starts.  Measurement and tests. */
+int  gx_edit_info(const gx_context* ctx, uint64_t* candidates, uint64_t* pre_dedupe_ends, uint64_t* cell_updates,
+                  double* seed_ms, double* verify_ms, double* dedupe_ms);
+
 #ifdef __cplusplus
 }
 #endif
