@@ -10,6 +10,7 @@
 //   gx_api_compare.cpp  compare mode: longest-common-substring recursion (main.rs:216-379)
 //   gx_api_suffix.cpp   suffix-tree mode: BWT and tree statistics from the suffix array (main.rs:154-215)
 //   gx_api_search.cpp   search mode: a kept suffix index and batched exact-match and k-mismatch queries on it
+//   gx_api_match.cpp    search mode: matching statistics and maximal exact matches of long queries
 // Not a public header: host code only, one library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -344,7 +345,20 @@ struct gx_context {
     // the last edit search (gx_edit_info; gx_api_search.cpp)
     uint64_t edit_cands = 0, edit_ends = 0, edit_cells = 0;
     double edit_seed_ms = 0.0, edit_verify_ms = 0.0, edit_dedupe_ms = 0.0;
+    // the last matching-statistics or MEM call (gx_match_info; gx_api_match.cpp)
+    uint64_t mat_cands = 0, mat_kept = 0, mat_words = 0;
+    double mat_stats_ms = 0.0, mat_seed_ms = 0.0, mat_emit_ms = 0.0;
 };
+
+// search mode's index (gx_api_search.cpp builds and frees it; gx_api_match.cpp reads it)
+struct gx_suffix_index {
+    gx_context* ctx = nullptr;   // nullptr: a host index
+    uint64_t n = 0;
+    std::vector<uint8_t> text;   // host index: t and kSufPad zero bytes
+    std::vector<uint32_t> sa;    // host index
+    DevBuf d_text, d_sa;         // device index: held out of the pool until the index is freed
+};
+uint64_t approx_budget();   // GX_APPROX_CAND_BUDGET (gx_api_search.cpp)
 
 struct PairHost {
     const uint8_t* s1;   // original bytes (traceback labels, sequence.rs:113 with rev=false)

@@ -26,14 +26,6 @@
 #include "gx_edit.h"
 #include "gx_search.h"
 
-struct gx_suffix_index {
-    gx_context* ctx = nullptr;   // nullptr: a host index
-    uint64_t n = 0;
-    std::vector<uint8_t> text;   // host index: t and kSufPad zero bytes
-    std::vector<uint32_t> sa;    // host index
-    DevBuf d_text, d_sa;         // device index: held out of the pool until the index is freed
-};
-
 namespace {
 
 static_assert(sizeof(gx_search_hit) == sizeof(SrchHit), "gx_search_hit layout");
@@ -231,7 +223,10 @@ int check_batch(const uint8_t* patterns, const uint64_t* offsets, size_t npat) {
 static_assert(sizeof(gx_approx_hit) == sizeof(AprxHit), "gx_approx_hit layout");
 static_assert(GX_APPROX_MAX_K == kAprxMaxK, "GX_APPROX_MAX_K");
 
-// GX_APPROX_CAND_BUDGET, read on every call: seed hits a batch may have.
+}  // namespace
+
+// GX_APPROX_CAND_BUDGET, read on every call: seed hits a batch may have (gx_api.h: the MEM search holds its
+// candidates against it too).
 uint64_t approx_budget() {
     uint64_t b = 1ull << 27;
     if (const char* e = getenv("GX_APPROX_CAND_BUDGET")) {
@@ -241,6 +236,8 @@ uint64_t approx_budget() {
     }
     return std::min<uint64_t>(b, 1ull << 31);
 }
+
+namespace {
 
 int budget_error(uint64_t total, uint64_t budget) {
     return fail(GX_ERANGE, "approximate search: " + std::to_string(total) + " seed hits, more than GX_APPROX_CAND_BUDGET = " +

@@ -52,6 +52,12 @@
 //       most that many substitutions, insertions and deletions
 //       (gx_suffix_index_search_edit); the line is then name,
 //       length, count, best_dist, best_end and up to K start-end:dist triples.
+//   gx-align search -f genome.fasta -p queries.fasta --mem L [-o mems.tsv]
+//       (not together with -k or -e) Every maximal exact match of L bases or
+//       more between a record of queries.fasta, of any length, and the genome
+//       (gx_suffix_index_mems).  One line per MEM: query name,
+//       qpos, tpos, len (0-based), by query, then qpos, then tpos; after them
+//       one line per query without a MEM: name, -, -, 0.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -77,7 +83,8 @@ void usage() {
             "       gx-align compare -d|--fasta-dir <DIR> [-o <TSV>]\n"
             "       gx-align suffix-tree -f|--fasta-path <FASTA> [-a|--alphabet-file <ALPHABET>] [--suffix-links] "
             "[--stats] [-o <BWT>]\n"
-            "       gx-align search -f|--fasta-path <GENOME> -p|--patterns <PATTERNS> [--max-hits <K>] [-k <MISMATCHES> | -e <EDITS>] [-o <TSV>]\n");
+            "       gx-align search -f|--fasta-path <GENOME> -p|--patterns <PATTERNS> [--max-hits <K>] [-k <MISMATCHES> | -e <EDITS>] [-o <TSV>]\n"
+            "       gx-align search -f|--fasta-path <GENOME> -p|--patterns <QUERIES> --mem <MIN_LEN> [-o <TSV>]\n");
 }
 
 struct Records {
@@ -560,6 +567,61 @@ int run_search(const std::string& fasta, const std::string& patterns, uint32_t m
     return 0;
 }
 
+// search --mem L on GPU 0: the MEMs of every record of the query file against the genome's first record.
+int run_mems(const std::string& fasta, const std::string& queries, uint32_t min_len, const std::string& out_path) {
+    const char* lg = getenv("GX_LOG");
+    const bool info = lg && (!strcmp(lg, "info") || !strcmp(lg, "debug"));
+    if (info) fprintf(stderr, "[INFO] MODE: Search (MEMs)\n[INFO] Loading sequences from %s and %s\n", fasta.c_str(), queries.c_str());
+    Records g, q;
+    load_fasta(fasta, g);
+    load_fasta(queries, q);
+    if (!g.size()) { fprintf(stderr, "[ERROR] no record in %s\n", fasta.c_str()); return 1; }
+    const size_t nq = q.size();
+    std::vector<uint8_t> packed;
+    std::vector<uint64_t> off(nq + 1, 0), moff(nq + 1, 0), cand(nq + 1, 0);
+    for (size_t c = 0; c < nq; ++c) {
+        packed.insert(packed.end(), q.seq(c), q.seq(c) + q.sl[c]);
+        off[c + 1] = packed.size();
+    }
+    gx_context* ctx = nullptr;
+    if (gx_context_create(0, &ctx) != GX_OK) return fail_msg("context", 1);
+    gx_suffix_index* idx = nullptr;
+    auto t0 = std::chrono::steady_clock::now();
+    int rc = gx_suffix_index_build(ctx, g.seq(0), g.sl[0], &idx);
+    if (rc != GX_OK) { gx_context_destroy(ctx); return fail_msg("search: index", rc); }
+    const auto build_us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+    std::vector<gx_mem> mems;
+    t0 = std::chrono::steady_clock::now();
+    // the counts first, then the exact capacity
+    rc = gx_suffix_index_mems(idx, packed.data(), off.data(), nq, min_len, nullptr, 0, moff.data(), cand.data());
+    if (rc == GX_OK && moff[nq]) {
+        mems.resize((size_t)moff[nq]);
+        rc = gx_suffix_index_mems(idx, packed.data(), off.data(), nq, min_len, mems.data(), mems.size(), moff.data(), cand.data());
+    }
+    const auto us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+    if (rc == GX_OK && info) {
+        uint64_t cands = 0, kept = 0, words = 0;
+        double tms = 0, sms = 0, ems = 0;
+        gx_match_info(ctx, &cands, &kept, &words, &tms, &sms, &ems);
+        fprintf(stderr, "[INFO] index of %llu bases built in %lld us; %zu queries of %llu bases matched at min_len %u in %lld us "
+                        "(%llu candidates, %llu MEMs, %llu word compares, seeds %.3f ms, emit %.3f ms)\n",
+                (unsigned long long)g.sl[0], (long long)build_us, nq, (unsigned long long)off[nq], min_len, (long long)us,
+                (unsigned long long)cands, (unsigned long long)kept, (unsigned long long)words, sms, ems);
+    }
+    gx_suffix_index_free(idx);
+    gx_context_destroy(ctx);
+    if (rc != GX_OK) return fail_msg("search --mem", rc);
+    FILE* f = out_path.empty() ? stdout : fopen(out_path.c_str(), "w");
+    if (!f) { fprintf(stderr, "[ERROR] cannot write %s\n", out_path.c_str()); return 1; }
+    for (size_t c = 0; c < nq; ++c)
+        for (uint64_t k = moff[c]; k < moff[c + 1]; ++k)
+            fprintf(f, "%s\t%u\t%u\t%u\n", q.name(c).c_str(), mems[k].qpos, mems[k].tpos, mems[k].len);
+    for (size_t c = 0; c < nq; ++c)
+        if (moff[c + 1] == moff[c]) fprintf(f, "%s\t-\t-\t0\n", q.name(c).c_str());
+    if (f != stdout) fclose(f);
+    return 0;
+}
+
 }  // namespace
 
 int main(int argc, char** argv) {
@@ -567,7 +629,7 @@ int main(int argc, char** argv) {
     setenv("GX_LOG", getenv("GX_LOG") ? getenv("GX_LOG") : "info", 1);
     std::string config = "config.toml", type, fasta, dir, tsv = "similarity_matrix.tsv", mode, patterns;
     int ngpu = 0;
-    long long max_hits = 16, kmis = -1, kedit = -1;
+    long long max_hits = 16, kmis = -1, kedit = -1, mem_len = -1;
     bool with_self = true, stats = false, out_set = false;
     for (int k = 1; k < argc; ++k) {
         std::string a = argv[k];
@@ -586,6 +648,7 @@ int main(int argc, char** argv) {
         else if (a == "--max-hits") { std::string v; next(v); max_hits = atoll(v.c_str()); }
         else if (a == "-k" || a == "--mismatches") { std::string v; next(v); kmis = atoll(v.c_str()); if (kmis < 0) { usage(); return 2; } }
         else if (a == "-e" || a == "--edits") { std::string v; next(v); kedit = atoll(v.c_str()); if (kedit < 0) { usage(); return 2; } }
+        else if (a == "--mem") { std::string v; next(v); mem_len = atoll(v.c_str()); if (mem_len < 1 || mem_len > 0xFFFFFFFFll) { usage(); return 2; } }
         else if (a == "--suffix-links") {}   // (the reference's build strategy: no counterpart)
         else if (a == "-g" || a == "--gpus") { std::string v; next(v); ngpu = atoi(v.c_str()); }
         else if (a == "--no-self") with_self = false;
@@ -595,11 +658,12 @@ int main(int argc, char** argv) {
     const bool by_file = mode == "align" || mode == "suffix-tree" || mode == "search";
     if (mode.empty() || (by_file && fasta.empty()) || (!by_file && dir.empty()) ||
         (mode == "search" && (patterns.empty() || max_hits < 0 || max_hits > 0xFFFFFFFFll || kmis > 0xFFFF || kedit > 0xFFFF ||
-                              (kmis >= 0 && kedit >= 0)))) {
+                              (kmis >= 0 && kedit >= 0) || (mem_len >= 0 && (kmis >= 0 || kedit >= 0))))) {
         usage();
         return 2;
     }
     if (mode == "compare") return run_compare(dir, tsv);   // (reads no scores: main.rs:216-221)
+    if (mode == "search" && mem_len >= 0) return run_mems(fasta, patterns, (uint32_t)mem_len, out_set ? tsv : std::string());
     if (mode == "search") return run_search(fasta, patterns, (uint32_t)max_hits, out_set ? tsv : std::string(), (int)kmis, (int)kedit);
     if (mode == "suffix-tree") return run_suffix_tree(fasta, type, stats, out_set ? tsv : std::string());
     gx_scores sc;

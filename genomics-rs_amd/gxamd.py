@@ -98,7 +98,8 @@ EXPORTED = ["gx_last_error", "gx_version", "gx_context_create", "gx_context_dest
             "gx_suffix_tree_stats", "gx_suffix_info", "gx_suffix_digit_passes", "gx_suffix_tile", "gx_format_suffix_stats",
             "gx_suffix_index_build", "gx_suffix_index_free", "gx_suffix_index_info", "gx_suffix_index_export",
             "gx_suffix_index_search", "gx_search_info", "gx_suffix_index_search_approx", "gx_approx_info",
-            "gx_suffix_index_search_edit", "gx_edit_info"]
+            "gx_suffix_index_search_edit", "gx_edit_info",
+            "gx_suffix_index_match_stats", "gx_suffix_index_mems", "gx_match_info"]
 
 _lib = None
 
@@ -199,6 +200,9 @@ def lib():
     L.gx_approx_info.argtypes = [vp, u64p, u64p, dp, dp]
     L.gx_suffix_index_search_edit.argtypes = [vp, vp, vp, sz, ctypes.c_uint32, vp, ctypes.c_uint32, vp, vp, vp, sz, vp]
     L.gx_edit_info.argtypes = [vp, u64p, u64p, u64p, dp, dp, dp]
+    L.gx_suffix_index_match_stats.argtypes = [vp, vp, vp, sz, ctypes.c_uint32, vp]
+    L.gx_suffix_index_mems.argtypes = [vp, vp, vp, sz, ctypes.c_uint32, vp, sz, vp, vp]
+    L.gx_match_info.argtypes = [vp, u64p, u64p, u64p, dp, dp, dp]
     _lib = L
     return L
 
@@ -1052,6 +1056,8 @@ def suffix_tile() -> Tuple[int, int, int]:
 HIT_DTYPE = np.dtype([("lo", "<u4"), ("count", "<u4"), ("prefix_len", "<u4"), ("prefix_pos", "<u4")])
 APPROX_HIT_DTYPE = np.dtype([("count", "<u4"), ("best_dist", "<u4"), ("best_pos", "<u4"), ("candidates", "<u4")])
 EDIT_HIT_DTYPE = np.dtype([("count", "<u4"), ("best_dist", "<u4"), ("best_end", "<u4"), ("candidates", "<u4")])
+MATCH_STAT_DTYPE = np.dtype([("len", "<u4"), ("lo", "<u4"), ("count", "<u4"), ("pos", "<u4")])
+MEM_DTYPE = np.dtype([("qpos", "<u4"), ("tpos", "<u4"), ("len", "<u4")])
 APPROX_MAX_K = 8        # GX_APPROX_MAX_K
 EDIT_MAX_M = 4096       # GX_EDIT_MAX_M
 NO_DIST = 0xFFFFFFFF    # best_dist of a pattern without an occurrence
@@ -1182,6 +1188,47 @@ class SuffixIndex:
             r.update(out)
         return r
 
+    def matching_stats(self, queries, max_len: int = 65535) -> dict:
+        """gx_suffix_index_match_stats for a batch of long queries (`queries` as `patterns` of search, of any
+        length): for every position of every query the longest prefix of its window (max_len bytes at most)
+        that occurs in the text.  Returns uint32 arrays "len", "lo", "count", "pos" (one entry per query
+        position; query c's are at offsets[c]:offsets[c + 1]) and "offsets" (uint64, nq + 1)."""
+        packed, off, nq = self._batch(queries)
+        st = np.zeros(int(off[-1]), MATCH_STAT_DTYPE)
+        _check(lib().gx_suffix_index_match_stats(self.ptr, packed.ctypes.data, off.ctypes.data, nq, max_len,
+                                                 st.ctypes.data if st.size else None))
+        r = {f: np.ascontiguousarray(st[f]) for f in ("len", "lo", "count", "pos")}
+        r["offsets"] = off
+        return r
+
+    def mems(self, queries, min_len: int, max_mems: Optional[int] = None) -> dict:
+        """gx_suffix_index_mems for a batch of long queries: every maximal exact match of min_len bytes or
+        more between a query and the text.  Returns uint32 arrays "qpos", "tpos", "length" (query c's MEMs at
+        mem_offsets[c]:mem_offsets[c + 1], ordered by qpos, then tpos), "mem_offsets" (uint64, nq + 1) and
+        "candidates" (uint64, the pairs examined per query).  max_mems=0 asks for the counts only (empty
+        triples); None makes two calls, the counts first and then the exact capacity; a number is the
+        capacity of one call (GxError 7 when it is too small)."""
+        packed, off, nq = self._batch(queries)
+        moff, cand = np.zeros(nq + 1, np.uint64), np.zeros(nq, np.uint64)
+
+        def call(mem, cap):
+            _check(lib().gx_suffix_index_mems(self.ptr, packed.ctypes.data, off.ctypes.data, nq, min_len,
+                                              mem.ctypes.data if mem is not None else None, cap, moff.ctypes.data,
+                                              cand.ctypes.data if nq else None))
+
+        mem = np.zeros(0, MEM_DTYPE)
+        if max_mems is None or max_mems <= 0:
+            call(None, 0)
+            if max_mems is None and int(moff[-1]):
+                mem = np.zeros(int(moff[-1]), MEM_DTYPE)
+                call(mem, mem.size)
+        else:
+            mem = np.zeros(max_mems, MEM_DTYPE)
+            call(mem, max_mems)
+            mem = mem[:int(moff[-1])]
+        return {"qpos": np.ascontiguousarray(mem["qpos"]), "tpos": np.ascontiguousarray(mem["tpos"]),
+                "length": np.ascontiguousarray(mem["len"]), "mem_offsets": moff, "candidates": cand}
+
     def sa(self) -> np.ndarray:
         """The suffix array, n + 1 entries (gx_suffix_index_export)."""
         a = np.zeros(self.n + 1, np.uint32)
@@ -1235,6 +1282,18 @@ def edit_info(ctx: Optional["Context"] = None) -> dict:
     _check(lib().gx_edit_info(ctx.ptr, *[ctypes.byref(x) for x in v + ms]))
     return {"candidates": v[0].value, "pre_dedupe_ends": v[1].value, "cell_updates": v[2].value,
             "seed_ms": ms[0].value, "verify_ms": ms[1].value, "dedupe_ms": ms[2].value}
+
+
+def match_info(ctx: Optional["Context"] = None) -> dict:
+    """gx_match_info of the last matching-statistics or MEM call on ctx: candidate pairs, kept (left-maximal)
+    pairs, 8-byte compare steps, device ms of the matching-statistics kernel, of the seed stages and of emit,
+    sort and pack (0 for what did not run)."""
+    ctx = ctx or default_context()
+    v = [ctypes.c_uint64() for _ in range(3)]
+    ms = [ctypes.c_double() for _ in range(3)]
+    _check(lib().gx_match_info(ctx.ptr, *[ctypes.byref(x) for x in v + ms]))
+    return {"candidates": v[0].value, "kept": v[1].value, "word_compares": v[2].value,
+            "stats_ms": ms[0].value, "seed_ms": ms[1].value, "emit_ms": ms[2].value}
 
 
 # STRING_TERMINATORS (tree.rs:66-69)

@@ -607,6 +607,57 @@ int  gx_suffix_index_search_edit(gx_suffix_index* idx, const uint8_t* patterns, 
 int  gx_edit_info(const gx_context* ctx, uint64_t* candidates, uint64_t* pre_dedupe_ends, uint64_t* cell_updates,
                   double* seed_ms, double* verify_ms, double* dedupe_ms);
 
+/* ---- matching statistics and maximal exact matches ------------
+ * Long queries against the index: where a genome or a contig agrees with the
+ * text.  Conventions as above (t = s + '$', N = n + 1, unsigned byte order, every
+ * query byte above '$').  A call takes a batch of queries concatenated like
+ * patterns, of any length: query c is queries[offsets[c] .. offsets[c + 1]), of
+ * length m_c, and its positions j are relative to its own start.  The total
+ * query bytes stay below 2^32 - 2064: the device's offsets and scans are 32-bit
+ * and need room for the 16 bytes of padding and a scan tile (2,048) of rounding.
+ *
+ * Matching statistics of position j of query c, w = min(max_len, m_c - j):
+ *   len     the longest prefix of Q_c[j .. j + w) that occurs in s
+ *   lo, count  the suffix-array interval of that prefix: exactly the suffixes
+ *           that have Q_c[j .. j + len) as a prefix
+ *   pos     SA[lo]
+ * and len = 0 gives lo = 0, count = N, pos = SA[0] = n, as m = 0 above.  A lane
+ * compares up to w bytes a probe: max_len bounds its work.
+ *
+ * A MEM of query c is (tpos = i, qpos = j, len) with len >= min_len,
+ * s[i .. i + len) = Q_c[j .. j + len), left-maximal (i = 0 or j = 0 or
+ * s[i - 1] != Q_c[j - 1]) and right-maximal (i + len = n or j + len = m_c or
+ * s[i + len] != Q_c[j + len]).  A match never contains '$' and never crosses
+ * into a neighbouring query.  Every such triple is reported exactly once,
+ * overlapping ones and those on one diagonal included; within a query they are
+ * ordered by qpos, then tpos.  The candidates of a query are the (i, j) pairs
+ * examined for it: every occurrence in s of every min_len-mer of the query. */
+typedef struct gx_match_stat { uint32_t len, lo, count, pos; } gx_match_stat;
+typedef struct gx_mem        { uint32_t qpos, tpos, len; } gx_mem;
+
+/* stats[offsets[c] + j] for position j of query c.  Errors: GX_EINVAL (a query
+ * byte at or below '$', query and offset named; bad offsets; max_len = 0; NULL
+ * stats), GX_ERANGE (total query bytes + 2064 at or above 2^32, as above). */
+int  gx_suffix_index_match_stats(gx_suffix_index* idx, const uint8_t* queries, const uint64_t* offsets /* nq+1 */,
+                                 size_t nq, uint32_t max_len, gx_match_stat* stats /* offsets[nq] entries */);
+/* The MEMs of query c at [mem_offsets[c], mem_offsets[c + 1]) of mems[];
+ * candidates[c] as above.  mems = NULL: counts only (mem_offsets and candidates).
+ * Errors as above (min_len = 0, NULL mem_offsets: GX_EINVAL), and GX_ERANGE: the
+ * candidates of the batch come to more than GX_APPROX_CAND_BUDGET (read on every
+ * call; 12 pooled device bytes a candidate, 36 a kept pair): nothing further runs and only
+ * candidates[] is written.  GX_ECAP: mems_cap is below the total (named);
+ * mem_offsets[] and candidates[] are complete, mems[] is untouched. */
+int  gx_suffix_index_mems(gx_suffix_index* idx, const uint8_t* queries, const uint64_t* offsets /* nq+1 */,
+                          size_t nq, uint32_t min_len, gx_mem* mems /* may be NULL: counts only */,
+                          size_t mems_cap, uint64_t* mem_offsets /* nq+1 */, uint64_t* candidates /* nq, may be NULL */);
+/* The last matching-statistics or MEM call on ctx: candidate pairs, kept
+ * (left-maximal) pairs, the 8-byte compare steps of its kernels, and device time
+ * (ms) of the matching-statistics kernel, of the seed stages (interval kernel,
+ * scan, keep, counts) and of emit, sort and pack.  What did not run is 0.
+ * Measurement and tests. */
+int  gx_match_info(const gx_context* ctx, uint64_t* candidates, uint64_t* kept, uint64_t* word_compares,
+                   double* stats_ms, double* seed_ms, double* emit_ms);
+
 #ifdef __cplusplus
 }
 #endif
