@@ -11,6 +11,7 @@
 //   gx_api_suffix.cpp   suffix-tree mode: BWT and tree statistics from the suffix array (main.rs:154-215)
 //   gx_api_search.cpp   search mode: a kept suffix index and batched exact-match and k-mismatch queries on it
 //   gx_api_match.cpp    search mode: matching statistics and maximal exact matches of long queries
+// gx_api_call.h adds the scope of one device call (DevCall, GX_TRY, GX_GET) for the drivers of the last four.
 // Not a public header: host code only, one library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -359,6 +360,21 @@ struct gx_suffix_index {
     DevBuf d_text, d_sa;         // device index: held out of the pool until the index is freed
 };
 uint64_t approx_budget();   // GX_APPROX_CAND_BUDGET (gx_api_search.cpp)
+// What search mode refuses of a batch of patterns or queries before a byte is staged (gx_api_search.cpp).
+struct BatchKind {
+    const char* noun;     // "pattern", "query": an item in the messages
+    const char* plural;   // ... and the argument that holds their bytes
+    uint64_t item_max;    // an item's most bytes (0: any)
+    bool positions;       // every byte is a position of the device's 32-bit scans (the long queries' range rule)
+};
+int check_batch(const BatchKind& kind, const uint8_t* bytes, const uint64_t* offsets, size_t n);
+// A checked batch as the drivers take it: offsets in 32 bits, and for a host index the bytes with kSufPad zero
+// bytes behind them (a device index pads on the device).
+struct HostBatch {
+    std::vector<uint32_t> offs;
+    std::vector<uint8_t> padded;
+};
+void narrow_batch(const gx_suffix_index* idx, const uint8_t* bytes, const uint64_t* offsets, size_t n, HostBatch& b);
 
 struct PairHost {
     const uint8_t* s1;   // original bytes (traceback labels, sequence.rs:113 with rev=false)

@@ -11,7 +11,7 @@
 //                 string (the suffix tree's DFS order)
 //   level driver  compare_core: the recursion of every pair level by level,
 //                 one batch of launches (gx_lcsub.hip) per level
-#include "gx_api.h"
+#include "gx_api_call.h"
 #include "gx_lcsub.h"
 
 namespace {
@@ -224,50 +224,37 @@ int gpu_batch(Cmp& c, const Sub* subs, size_t nsub, std::vector<Sub>& next) {
     if (tiles >= (1ull << 31)) return fail(GX_ERANGE, "compare: too many tiles in one launch");
     const size_t small_words = 4 + 3 * nsub;   // hdr[4], L, cnt, ovf
     const size_t slots = nsub * (size_t)c.cap;
-    DevBuf d_desc, d_elem, d_carry, d_small, d_cand;
-    auto done = [&](int rc) {
-        if (rc != GX_OK) (void)hipStreamSynchronize(st);   // nothing of this batch still runs on the buffers
-        for (DevBuf* b : {&d_desc, &d_elem, &d_carry, &d_small, &d_cand}) pool_put(ctx, *b);
-        return rc;
-    };
-#define CMP_TRY(expr)                                                                                         \
-    do {                                                                                                      \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess)                                                                                 \
-            return done(fail(e_ == hipErrorOutOfMemory ? GX_ENOMEM : GX_EHIP,                                 \
-                             std::string(#expr) + ": " + hipGetErrorString(e_)));                             \
-    } while (0)
-    int rc;
-    if ((rc = pool_get(ctx, nsub * sizeof(LcsubDesc), &d_desc, st)) != GX_OK) return done(rc);
-    if ((rc = pool_get(ctx, elems * sizeof(uint2), &d_elem, st)) != GX_OK) return done(rc);
-    if ((rc = pool_get(ctx, elems * sizeof(unsigned), &d_carry, st)) != GX_OK) return done(rc);
-    if ((rc = pool_get(ctx, small_words * sizeof(unsigned), &d_small, st)) != GX_OK) return done(rc);
-    if ((rc = pool_get(ctx, slots * sizeof(uint4), &d_cand, st)) != GX_OK) return done(rc);
+    DevCall call(ctx);
+    LcsubDesc* d_desc = nullptr;
+    uint2* d_elem = nullptr;
+    unsigned *d_carry = nullptr, *d_hdr = nullptr;
+    uint4* d_cand = nullptr;
+    GX_GET(call, d_desc, nsub);
+    GX_GET(call, d_elem, elems);
+    GX_GET(call, d_carry, elems);
+    GX_GET(call, d_hdr, small_words);
+    GX_GET(call, d_cand, slots);
     // pinned staging: [descriptors][small words], later the candidates that were written
     const size_t off_small = align_up(nsub * sizeof(LcsubDesc), 16);
     uint8_t* pin = (uint8_t*)io_pinned(ctx, off_small + small_words * sizeof(unsigned));
-    if (!pin) return done(fail(GX_ENOMEM, "compare: pinned staging"));
+    if (!pin) return call.done(fail(GX_ENOMEM, "compare: pinned staging"));
     memcpy(pin, desc.data(), nsub * sizeof(LcsubDesc));
-    unsigned* d_hdr = (unsigned*)d_small.p;
     unsigned* d_L = d_hdr + 4;
     unsigned* d_cnt = d_L + nsub;
     unsigned* d_ovf = d_cnt + nsub;
     const int cus = fill_grid_cap(ctx->device);
     const int grid_t = (int)std::min<uint64_t>(tiles, (uint64_t)cus * 8);
     const int grid_d = (int)std::min<uint64_t>(dtiles, (uint64_t)cus * 8);
-    CMP_TRY(hipMemcpyAsync(d_desc.p, pin, nsub * sizeof(LcsubDesc), hipMemcpyHostToDevice, st));
-    CMP_TRY(hipMemsetAsync(d_small.p, 0, small_words * sizeof(unsigned), st));
-    CMP_TRY(hipEventRecord(ctx->ev0, st));
-    CMP_TRY(launch_lcsub_run((const uint8_t*)c.chars.p, (const LcsubDesc*)d_desc.p, (int)nsub, (unsigned)tiles, c.H,
-                             (uint2*)d_elem.p, grid_t, st));
-    CMP_TRY(hipEventRecord(ctx->ev1, st));
-    CMP_TRY(launch_lcsub_combine((const LcsubDesc*)d_desc.p, (int)nsub, (unsigned)dtiles, (const uint2*)d_elem.p,
-                                 (unsigned*)d_carry.p, d_L, grid_d, st));
-    CMP_TRY(launch_lcsub_cand((const uint8_t*)c.chars.p, (const LcsubDesc*)d_desc.p, (int)nsub, (unsigned)tiles, c.H,
-                              (const uint2*)d_elem.p, (const unsigned*)d_carry.p, d_L, c.cap, (unsigned)slots, d_cnt,
-                              d_ovf, d_hdr, (uint4*)d_cand.p, grid_t, st));
-    CMP_TRY(hipMemcpyAsync(pin + off_small, d_small.p, small_words * sizeof(unsigned), hipMemcpyDeviceToHost, st));
-    CMP_TRY(hipStreamSynchronize(st));
+    GX_TRY(call, hipMemcpyAsync(d_desc, pin, nsub * sizeof(LcsubDesc), hipMemcpyHostToDevice, st));
+    GX_TRY(call, hipMemsetAsync(d_hdr, 0, small_words * sizeof(unsigned), st));
+    GX_TRY(call, hipEventRecord(ctx->ev0, st));
+    GX_TRY(call, launch_lcsub_run((const uint8_t*)c.chars.p, d_desc, (int)nsub, (unsigned)tiles, c.H, d_elem, grid_t, st));
+    GX_TRY(call, hipEventRecord(ctx->ev1, st));
+    GX_TRY(call, launch_lcsub_combine(d_desc, (int)nsub, (unsigned)dtiles, d_elem, d_carry, d_L, grid_d, st));
+    GX_TRY(call, launch_lcsub_cand((const uint8_t*)c.chars.p, d_desc, (int)nsub, (unsigned)tiles, c.H, d_elem, d_carry, d_L,
+                                   c.cap, (unsigned)slots, d_cnt, d_ovf, d_hdr, d_cand, grid_t, st));
+    GX_TRY(call, hipMemcpyAsync(pin + off_small, d_hdr, small_words * sizeof(unsigned), hipMemcpyDeviceToHost, st));
+    GX_TRY(call, hipStreamSynchronize(st));
     const std::vector<unsigned> small((const unsigned*)(pin + off_small),
                                       (const unsigned*)(pin + off_small) + small_words);
     const unsigned* h_small = small.data();
@@ -275,16 +262,16 @@ int gpu_batch(Cmp& c, const Sub* subs, size_t nsub, std::vector<Sub>& next) {
     const uint4* h_cand = nullptr;
     if (ncand) {
         pin = (uint8_t*)io_pinned(ctx, ncand * sizeof(uint4));   // (may move: the small words were copied out)
-        if (!pin) return done(fail(GX_ENOMEM, "compare: pinned staging"));
-        CMP_TRY(hipMemcpyAsync(pin, d_cand.p, ncand * sizeof(uint4), hipMemcpyDeviceToHost, st));
-        CMP_TRY(hipStreamSynchronize(st));
+        if (!pin) return call.done(fail(GX_ENOMEM, "compare: pinned staging"));
+        GX_TRY(call, hipMemcpyAsync(pin, d_cand, ncand * sizeof(uint4), hipMemcpyDeviceToHost, st));
+        GX_TRY(call, hipStreamSynchronize(st));
         h_cand = (const uint4*)pin;
     }
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) c.run_ms += ms;
+    double ms = 0.0;
+    call.elapsed(ctx->ev0, ctx->ev1, &ms);
+    c.run_ms += ms;
     c.cells += cells;
-    done(GX_OK);   // (the stream is idle)
-#undef CMP_TRY
+    call.done(GX_OK);   // (the stream is idle)
     // candidates by sub-problem (they arrive in no order)
     const unsigned* h_L = h_small + 4;
     const unsigned* h_ovf = h_L + 2 * nsub;

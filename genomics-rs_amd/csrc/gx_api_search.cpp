@@ -21,16 +21,100 @@
 //                  band of gx_edit.h on every seed hit, the reported ends sorted
 //                  and each run's minimum kept, then the starts of the reported
 //                  occurrences.  Device: gx_edit.hip
-#include "gx_api.h"
+//   shared stages  what the three searches and the long-query calls of
+//                  gx_api_match.cpp have in common: the batch
+//                  checker, the prologue of the entry points, stage_batch, the
+//                  seeds of both sides, the epilogue that copies exactly the total
+#include "gx_api_call.h"
 #include "gx_approx.h"
 #include "gx_edit.h"
 #include "gx_search.h"
+
+// ---------------------------------------------------------------------------
+// shared with gx_api_match.cpp (declared in gx_api.h and gx_api_call.h)
+
+// GX_APPROX_CAND_BUDGET, read on every call: seed hits a batch may have (gx_api.h: the MEM search holds its
+// candidates against it too).
+uint64_t approx_budget() {
+    uint64_t b = 1ull << 27;
+    if (const char* e = getenv("GX_APPROX_CAND_BUDGET")) {
+        char* end = nullptr;
+        const unsigned long long v = strtoull(e, &end, 10);
+        if (end != e && v > 0) b = v;
+    }
+    return std::min<uint64_t>(b, 1ull << 31);
+}
+
+// What every call of search mode refuses of a batch before a byte is staged.
+int check_batch(const BatchKind& kind, const uint8_t* bytes, const uint64_t* offsets, size_t n) {
+    const std::string noun = kind.noun;
+    if (offsets[0] != 0) return fail(GX_EINVAL, "offsets[0] is not 0");
+    for (size_t p = 0; p < n; ++p) {
+        if (offsets[p + 1] < offsets[p]) return fail(GX_EINVAL, "offsets decrease at " + noun + " " + std::to_string(p));
+        if (kind.item_max && offsets[p + 1] - offsets[p] > kind.item_max)
+            return fail(GX_ERANGE, noun + " " + std::to_string(p) + " has " + std::to_string(offsets[p + 1] - offsets[p]) +
+                                       " bytes, more than " + std::to_string(kind.item_max));
+    }
+    const uint64_t total = offsets[n];
+    if (kind.positions) {
+        // (the device's offsets and scans are 32-bit: the positions plus one, the scan's tile rounding and the padding)
+        if (total + kSufTile + kSufPad >= (1ull << 32) || (uint64_t)n + 1 + kSufTile >= (1ull << 32))
+            return fail(GX_ERANGE, "match: " + std::to_string(total) + " query bytes in " + std::to_string(n) +
+                                       " queries, 2^32 or more with the padding and the scan's tile rounding: split the batch");
+    } else {
+        // (one more than the 32-bit device offsets need, for the scan's n + 1 entries and its tile rounding)
+        if (total + n >= (1ull << 32) || (uint64_t)n + 1 + kSufTile >= (1ull << 32))
+            return fail(GX_ERANGE, "search: pattern bytes plus patterns come to " + std::to_string(total + n) +
+                                       ", 2^32 or more: split the batch or lower max_hits");
+    }
+    if (total && !bytes) return fail(GX_EINVAL, std::string(kind.plural) + " is NULL");
+    // (one flat pass the compiler vectorises; the culprit is looked for only when there is one)
+    unsigned low = 0;
+    for (uint64_t k = 0; k < total; ++k) low |= bytes[k] <= 0x24;
+    for (size_t p = 0; low && p < n; ++p)
+        for (uint64_t k = offsets[p]; k < offsets[p + 1]; ++k)
+            if (bytes[k] <= 0x24)
+                return fail(GX_EINVAL, noun + " " + std::to_string(p) + ": byte " + std::to_string((int)bytes[k]) +
+                                           " at offset " + std::to_string(k - offsets[p]) + " is not above '$'");
+    return GX_OK;
+}
+
+void narrow_batch(const gx_suffix_index* idx, const uint8_t* bytes, const uint64_t* offsets, size_t n, HostBatch& b) {
+    b.offs.resize(n + 1);
+    for (size_t p = 0; p <= n; ++p) b.offs[p] = (uint32_t)offsets[p];
+    if (idx->ctx) return;
+    // the host compares read 8 bytes at a time too: the same padding behind the bytes
+    const uint64_t total = offsets[n];
+    b.padded.assign(total + kSufPad, 0);
+    if (total) memcpy(b.padded.data(), bytes, total);
+}
+
+int stage_batch(DevCall& call, const char* what, const uint8_t* src, size_t total_bytes, const uint32_t* offs, uint32_t n,
+                StagedBatch& b) {
+    uint8_t* bytes = nullptr;
+    uint32_t* off = nullptr;
+    GX_GET(call, bytes, total_bytes + kSufPad);
+    GX_GET(call, off, (size_t)n + 1);
+    GX_GET(call, b.cnt, 8);
+    // (no copy of 0 bytes from a pointer that may be NULL)
+    if (total_bytes) GX_TRY(call, hipMemcpyAsync(bytes, src, total_bytes, hipMemcpyHostToDevice, call.st));
+    GX_TRY(call, hipMemsetAsync(bytes + total_bytes, 0, kSufPad, call.st));
+    GX_TRY(call, hipMemcpyAsync(off, offs, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, call.st));
+    GX_TRY(call, hipMemsetAsync(b.cnt, 0, 64, call.st));
+    b.pin = (unsigned long long*)io_pinned(call.ctx, 128);
+    if (!b.pin) return call.done(fail(GX_ENOMEM, std::string(what) + ": pinned staging"));
+    b.bytes = bytes;
+    b.off = off;
+    return GX_OK;
+}
 
 namespace {
 
 static_assert(sizeof(gx_search_hit) == sizeof(SrchHit), "gx_search_hit layout");
 
-// hit_offsets from hits (gx_search_hit or gx_approx_hit); returns the total.
+constexpr BatchKind kPatterns{"pattern", "patterns", kSrchMaxPattern, false};
+
+// hit_offsets from hits (gx_search_hit, gx_approx_hit or gx_edit_hit); returns the total.
 template <class Hit>
 uint64_t offsets_of(const Hit* hits, size_t npat, uint32_t max_hits, uint64_t* hit_offsets) {
     uint64_t tot = 0;
@@ -50,6 +134,35 @@ int cap_error(uint64_t total, size_t cap) {
 int total_error(uint64_t total) {
     return fail(GX_ERANGE, "search: " + std::to_string(total) +
                                " reported positions, 2^32 or more: split the batch or lower max_hits");
+}
+
+// One output array of a device search: the caller's (NULL: not asked for) and the device's, bytes per entry.
+struct OutCopy {
+    void* dst;
+    const void* src;
+    size_t elem;
+};
+
+// The end of a device search, hits[] already on the host and the stream idle: hit_offsets from the hits, and
+// when the first output is asked for, the refusals and the copy of exactly the total into every output that
+// is.  Only now is that number known to the host, so that GX_ECAP leaves the outputs untouched and the copies
+// move no more than them (a total above what the device reserved is above cap).
+template <class Hit>
+int finish_hits(DevCall& call, const Hit* hits, uint32_t npat, uint32_t max_hits, bool limit32, size_t cap,
+                uint64_t* hit_offsets, std::initializer_list<OutCopy> out) {
+    if (!out.begin()->dst) {
+        if (hit_offsets) offsets_of(hits, npat, max_hits, hit_offsets);
+        return call.done(GX_OK);
+    }
+    const uint64_t total = offsets_of(hits, npat, max_hits, hit_offsets);
+    if (limit32 && total >= (1ull << 32)) return call.done(total_error(total));
+    if (total > cap) return call.done(cap_error(total, cap));
+    if (total) {
+        for (const OutCopy& c : out)
+            if (c.dst) GX_TRY(call, hipMemcpyAsync(c.dst, c.src, (size_t)total * c.elem, hipMemcpyDeviceToHost, call.st));
+        GX_TRY(call, hipStreamSynchronize(call.st));
+    }
+    return call.done(GX_OK);   // (the stream is idle)
 }
 
 void sort_segments(uint32_t* positions, const uint64_t* hit_offsets, size_t npat) {
@@ -85,135 +198,68 @@ int search_device(gx_suffix_index* idx, const uint8_t* pats, size_t total_bytes,
     gx_context* ctx = idx->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
+    DevCall call(ctx);
+    hipStream_t st = call.st;
     const uint32_t N = (uint32_t)idx->n + 1;
     ctx->srch_words = 0;
     ctx->srch_ms = ctx->srch_locate_ms = 0.0;
-    DevBuf d_pat, d_off, d_hits, d_q, d_tmp, d_small, d_pos;
-    auto done = [&](int rc) {
-        if (rc != GX_OK) (void)hipStreamSynchronize(st);   // nothing of this call still runs on the buffers
-        for (DevBuf* b : {&d_pat, &d_off, &d_hits, &d_q, &d_tmp, &d_small, &d_pos}) pool_put(ctx, *b);
-        return rc;
-    };
-#define SR_TRY(expr)                                                                                          \
-    do {                                                                                                      \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess)                                                                                 \
-            return done(fail(e_ == hipErrorOutOfMemory ? GX_ENOMEM : GX_EHIP,                                 \
-                             std::string(#expr) + ": " + hipGetErrorString(e_)));                             \
-    } while (0)
-#define SR_GET(buf, bytes)                                                      \
-    do {                                                                        \
-        const int rc_ = pool_get(ctx, (bytes), &(buf), st);                     \
-        if (rc_ != GX_OK) return done(rc_);                                     \
-    } while (0)
     // 1. patterns and offsets, kSufPad zero bytes behind the patterns
-    SR_GET(d_pat, total_bytes + kSufPad);
-    SR_GET(d_off, ((size_t)npat + 1) * 4);
-    SR_GET(d_hits, (size_t)npat * sizeof(SrchHit));
-    SR_GET(d_small, 64);
-    unsigned long long* d_words = (unsigned long long*)d_small.p;
-    // (pageable sources: the copies have left them once the stream is synchronised below)
-    if (total_bytes) SR_TRY(hipMemcpyAsync(d_pat.p, pats, total_bytes, hipMemcpyHostToDevice, st));
-    SR_TRY(hipMemsetAsync((uint8_t*)d_pat.p + total_bytes, 0, kSufPad, st));
-    SR_TRY(hipMemcpyAsync(d_off.p, offs, ((size_t)npat + 1) * 4, hipMemcpyHostToDevice, st));
-    SR_TRY(hipMemsetAsync(d_words, 0, 8, st));
+    StagedBatch b;
+    if (const int rc = stage_batch(call, "search", pats, total_bytes, offs, npat, b)) return rc;
+    SrchHit* d_h = nullptr;
+    GX_GET(call, d_h, npat);
     // 2. the interval kernel
     const uint8_t* text = (const uint8_t*)idx->d_text.p;
     const uint32_t* sa = (const uint32_t*)idx->d_sa.p;
-    SrchHit* d_h = (SrchHit*)d_hits.p;
-    SR_TRY(hipEventRecord(ctx->ev0, st));
-    SR_TRY(launch_srch_range(text, sa, N, (const uint8_t*)d_pat.p, (const uint32_t*)d_off.p, npat, d_h, d_words, st));
-    SR_TRY(hipEventRecord(ctx->ev1, st));
-    unsigned long long* pin = (unsigned long long*)io_pinned(ctx, 128);
-    if (!pin) return done(fail(GX_ENOMEM, "search: pinned staging"));
+    GX_TRY(call, hipEventRecord(ctx->ev0, st));
+    GX_TRY(call, launch_srch_range(text, sa, N, b.bytes, b.off, npat, d_h, b.cnt, st));
+    GX_TRY(call, hipEventRecord(ctx->ev1, st));
     // what the positions can come to at most; the device's offsets are 32-bit,
     // so a batch that could reach 2^32 is summed on the host before the scan
     const uint64_t bound = (uint64_t)npat * std::min(max_hits, N);
     uint64_t dev_cap = std::min<uint64_t>(cap, bound);
     bool copied = false, located = false;
-    float ms = 0.f;
+    uint32_t* d_pos = nullptr;
     if (positions && bound >= (1ull << 32)) {
-        SR_TRY(hipMemcpyAsync(pin, d_words, 8, hipMemcpyDeviceToHost, st));
-        SR_TRY(hipMemcpyAsync(hits, d_h, (size_t)npat * sizeof(SrchHit), hipMemcpyDeviceToHost, st));
-        SR_TRY(hipStreamSynchronize(st));
+        GX_TRY(call, hipMemcpyAsync(b.pin, b.cnt, 8, hipMemcpyDeviceToHost, st));
+        GX_TRY(call, hipMemcpyAsync(hits, d_h, (size_t)npat * sizeof(SrchHit), hipMemcpyDeviceToHost, st));
+        GX_TRY(call, hipStreamSynchronize(st));
         copied = true;
-        if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) ctx->srch_ms = ms;
+        call.elapsed(ctx->ev0, ctx->ev1, &ctx->srch_ms);
         const uint64_t total = offsets_of(hits, npat, max_hits, nullptr);
         if (total >= (1ull << 32)) {
             offsets_of(hits, npat, max_hits, hit_offsets);
-            ctx->srch_words = pin[0];
-            return done(total_error(total));
+            ctx->srch_words = b.pin[0];
+            return call.done(total_error(total));
         }
         dev_cap = total <= cap ? total : 0;   // (the total is known here; above cap it is GX_ECAP below)
-        if (dev_cap) SR_TRY(hipEventRecord(ctx->ev1, st));   // the locate step starts here
+        if (dev_cap) GX_TRY(call, hipEventRecord(ctx->ev1, st));   // the locate step starts here
     }
     if (positions && dev_cap) {
         // 3. clamp, exclusive scan, gather: nothing else between ev1 and ev2
-        SR_GET(d_q, ((size_t)npat + 1) * 4);
-        SR_GET(d_tmp, suf_tiles((size_t)npat + 1) * 4);
-        SR_GET(d_pos, (size_t)dev_cap * 4);
-        uint32_t* q = (uint32_t*)d_q.p;
-        SR_TRY(launch_srch_clamp(d_h, npat, max_hits, q, st));
-        SR_TRY(launch_suf_scan(q, npat + 1, false, (uint32_t*)d_tmp.p, st));
-        SR_TRY(launch_srch_gather(sa, N, d_h, q, npat, (uint32_t*)d_pos.p, dev_cap, st));
-        SR_TRY(hipEventRecord(ctx->ev2, st));
+        uint32_t *q = nullptr, *tmp = nullptr;
+        GX_GET(call, q, (size_t)npat + 1);
+        GX_GET(call, tmp, suf_tiles((size_t)npat + 1));
+        GX_GET(call, d_pos, (size_t)dev_cap);
+        GX_TRY(call, launch_srch_clamp(d_h, npat, max_hits, q, st));
+        GX_TRY(call, launch_suf_scan(q, npat + 1, false, tmp, st));
+        GX_TRY(call, launch_srch_gather(sa, N, d_h, q, npat, d_pos, dev_cap, st));
+        GX_TRY(call, hipEventRecord(ctx->ev2, st));
         located = true;
     }
     if (!copied) {
         // (behind the last event, as suffix_device's copies: the events time kernels alone)
-        SR_TRY(hipMemcpyAsync(pin, d_words, 8, hipMemcpyDeviceToHost, st));
-        SR_TRY(hipMemcpyAsync(hits, d_h, (size_t)npat * sizeof(SrchHit), hipMemcpyDeviceToHost, st));
+        GX_TRY(call, hipMemcpyAsync(b.pin, b.cnt, 8, hipMemcpyDeviceToHost, st));
+        GX_TRY(call, hipMemcpyAsync(hits, d_h, (size_t)npat * sizeof(SrchHit), hipMemcpyDeviceToHost, st));
     }
-    SR_TRY(hipStreamSynchronize(st));
-    if (!copied && hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) ctx->srch_ms = ms;
-    if (located && hipEventElapsedTime(&ms, ctx->ev1, ctx->ev2) == hipSuccess) ctx->srch_locate_ms = ms;
-    ctx->srch_words = pin[0];
-    if (!positions) {
-        if (hit_offsets) offsets_of(hits, npat, max_hits, hit_offsets);
-        return done(GX_OK);
-    }
-    // 4. the positions: only now is their number known to the host, so that
-    // GX_ECAP leaves positions[] untouched and the copy moves no more than them
-    const uint64_t total = offsets_of(hits, npat, max_hits, hit_offsets);
-    if (total >= (1ull << 32)) return done(total_error(total));
-    if (total > cap) return done(cap_error(total, cap));
-    if (total) {
-        SR_TRY(hipMemcpyAsync(positions, d_pos.p, (size_t)total * 4, hipMemcpyDeviceToHost, st));
-        SR_TRY(hipStreamSynchronize(st));
-    }
-    done(GX_OK);   // (the stream is idle)
-#undef SR_TRY
-#undef SR_GET
-    sort_segments(positions, hit_offsets, npat);
-    return GX_OK;
-}
-
-// What both searches refuse of a batch before a pattern byte is staged.
-int check_batch(const uint8_t* patterns, const uint64_t* offsets, size_t npat) {
-    if (offsets[0] != 0) return fail(GX_EINVAL, "offsets[0] is not 0");
-    for (size_t p = 0; p < npat; ++p) {
-        if (offsets[p + 1] < offsets[p])
-            return fail(GX_EINVAL, "offsets decrease at pattern " + std::to_string(p));
-        if (offsets[p + 1] - offsets[p] > kSrchMaxPattern)
-            return fail(GX_ERANGE, "pattern " + std::to_string(p) + " has " + std::to_string(offsets[p + 1] - offsets[p]) +
-                                       " bytes, more than 65535");
-    }
-    const uint64_t total_bytes = offsets[npat];
-    // (one more than the 32-bit device offsets need, for the scan's npat + 1 entries and its tile rounding)
-    if (total_bytes + npat >= (1ull << 32) || (uint64_t)npat + 1 + kSufTile >= (1ull << 32))
-        return fail(GX_ERANGE, "search: pattern bytes plus patterns come to " + std::to_string(total_bytes + npat) +
-                                   ", 2^32 or more: split the batch or lower max_hits");
-    if (total_bytes && !patterns) return fail(GX_EINVAL, "patterns is NULL");
-    // (one flat pass the compiler vectorises; the culprit is looked for only when there is one)
-    unsigned low = 0;
-    for (uint64_t k = 0; k < total_bytes; ++k) low |= patterns[k] <= 0x24;
-    for (size_t p = 0; low && p < npat; ++p)
-        for (uint64_t k = offsets[p]; k < offsets[p + 1]; ++k)
-            if (patterns[k] <= 0x24)
-                return fail(GX_EINVAL, "pattern " + std::to_string(p) + ": byte " + std::to_string((int)patterns[k]) +
-                                           " at offset " + std::to_string(k - offsets[p]) + " is not above '$'");
-    return GX_OK;
+    GX_TRY(call, hipStreamSynchronize(st));
+    if (!copied) call.elapsed(ctx->ev0, ctx->ev1, &ctx->srch_ms);
+    if (located) call.elapsed(ctx->ev1, ctx->ev2, &ctx->srch_locate_ms);
+    ctx->srch_words = b.pin[0];
+    // 4. the positions
+    const int rc = finish_hits(call, hits, npat, max_hits, true, cap, hit_offsets, {{positions, d_pos, 4}});
+    if (rc == GX_OK && positions) sort_segments(positions, hit_offsets, npat);
+    return rc;
 }
 
 // ---------------------------------------------------------------------------
@@ -223,34 +269,85 @@ int check_batch(const uint8_t* patterns, const uint64_t* offsets, size_t npat) {
 static_assert(sizeof(gx_approx_hit) == sizeof(AprxHit), "gx_approx_hit layout");
 static_assert(GX_APPROX_MAX_K == kAprxMaxK, "GX_APPROX_MAX_K");
 
-}  // namespace
-
-// GX_APPROX_CAND_BUDGET, read on every call: seed hits a batch may have (gx_api.h: the MEM search holds its
-// candidates against it too).
-uint64_t approx_budget() {
-    uint64_t b = 1ull << 27;
-    if (const char* e = getenv("GX_APPROX_CAND_BUDGET")) {
-        char* end = nullptr;
-        const unsigned long long v = strtoull(e, &end, 10);
-        if (end != e && v > 0) b = v;
-    }
-    return std::min<uint64_t>(b, 1ull << 31);
-}
-
-namespace {
-
-int budget_error(uint64_t total, uint64_t budget) {
-    return fail(GX_ERANGE, "approximate search: " + std::to_string(total) + " seed hits, more than GX_APPROX_CAND_BUDGET = " +
+// what: "approximate search" or "edit search".
+int seed_budget_error(const char* what, uint64_t total, uint64_t budget) {
+    return fail(GX_ERANGE, std::string(what) + ": " + std::to_string(total) + " seed hits, more than GX_APPROX_CAND_BUDGET = " +
                                std::to_string(budget) + ": split the batch, lower k, or raise GX_APPROX_CAND_BUDGET");
 }
 
-// The budget refusal's only output: candidates per pattern from the pieces' intervals.
-void candidates_only(const SrchHit* ph, size_t npat, uint32_t k1, gx_approx_hit* hits) {
+// A budget refusal's only output: candidates per pattern from the pieces' intervals (gx_approx_hit or gx_edit_hit).
+template <class Hit>
+void candidates_only(const SrchHit* ph, size_t npat, uint32_t k1, Hit* hits) {
     for (size_t p = 0; p < npat; ++p) {
         uint64_t c = 0;
         for (uint32_t j = 0; j < k1; ++j) c += ph[p * k1 + j].count;
         hits[p].candidates = (uint32_t)std::min<uint64_t>(c, 0xFFFFFFFFull);
     }
+}
+
+// The seeds on the host: every piece of every pattern through the exact search, in candidate order, into ph[];
+// returns their 64-bit total.  pats: padded as for search_host.
+uint64_t seed_pieces_host(const gx_suffix_index* idx, const uint8_t* pats, const uint32_t* offs, size_t npat, uint32_t k1,
+                          std::vector<SrchHit>& ph, uint64_t* words) {
+    const uint32_t N = (uint32_t)idx->n + 1;
+    ph.resize(npat * k1);
+    uint64_t total = 0;
+    for (size_t p = 0; p < npat; ++p) {
+        const uint32_t m = offs[p + 1] - offs[p];
+        for (uint32_t j = 0; j < k1; ++j) {
+            const uint32_t ps = aprx_piece_start(m, k1, j), pe = aprx_piece_start(m, k1, j + 1);
+            ph[p * k1 + j] = srch_one(idx->text.data(), idx->sa.data(), N, pats + offs[p] + ps, pe - ps, words);
+            total += ph[p * k1 + j].count;
+        }
+    }
+    return total;
+}
+
+// The seeds on the device, DESIGN.md 19.2 stages 1 to 4: piece offsets, the pieces' intervals, their 64-bit
+// total, candidate offsets.
+struct DevSeeds {
+    uint32_t* poff = nullptr;   // npieces + 1 piece offsets
+    SrchHit* ph = nullptr;      // the pieces' intervals
+    uint32_t* coff = nullptr;   // npieces + 1 candidate offsets: relied upon only once the host has held the total
+                                // against the budget (the scan is 32-bit)
+    uint32_t* tmp = nullptr;    // the scan's, suf_tiles(npieces + 1) words
+    uint64_t total = 0;         // seed hits, also in b.pin[1] (b.pin[0]: the seeds' word steps)
+};
+// Between ev0 and ev1, then the read-back of the total; *seed_ms: the kernels alone.  Returns with the stream
+// idle; the budget is the caller's to hold the total against.
+int seed_pieces_device(DevCall& call, const gx_suffix_index* idx, const StagedBatch& b, uint32_t npat, uint32_t k1,
+                       double* seed_ms, DevSeeds& s) {
+    gx_context* ctx = call.ctx;
+    hipStream_t st = call.st;
+    const uint32_t N = (uint32_t)idx->n + 1, npieces = npat * k1;
+    GX_GET(call, s.poff, (size_t)npieces + 1);
+    GX_GET(call, s.ph, npieces);
+    GX_GET(call, s.coff, (size_t)npieces + 1);
+    GX_GET(call, s.tmp, suf_tiles((size_t)npieces + 1));
+    GX_TRY(call, hipEventRecord(ctx->ev0, st));
+    GX_TRY(call, launch_aprx_pieces(b.off, npat, k1, s.poff, st));
+    GX_TRY(call, launch_srch_range((const uint8_t*)idx->d_text.p, (const uint32_t*)idx->d_sa.p, N, b.bytes, s.poff, npieces,
+                                   s.ph, b.cnt, st));
+    GX_TRY(call, launch_aprx_total(s.ph, npieces, b.cnt + 1, st));
+    GX_TRY(call, launch_srch_clamp(s.ph, npieces, 0xFFFFFFFFu, s.coff, st));
+    GX_TRY(call, launch_suf_scan(s.coff, npieces + 1, false, s.tmp, st));
+    GX_TRY(call, hipEventRecord(ctx->ev1, st));
+    GX_TRY(call, hipMemcpyAsync(b.pin, b.cnt, 16, hipMemcpyDeviceToHost, st));
+    GX_TRY(call, hipStreamSynchronize(st));
+    call.elapsed(ctx->ev0, ctx->ev1, seed_ms);
+    s.total = b.pin[1];
+    return GX_OK;
+}
+
+// A budget refusal on the device: candidates_only from the pieces' intervals, then `rc` (the refusal, already
+// in gx_last_error) through done(); a failing read-back is reported in its place.
+template <class Hit>
+int refuse_device(DevCall& call, const DevSeeds& s, uint32_t npat, uint32_t k1, Hit* hits, int rc) {
+    std::vector<SrchHit> hp((size_t)npat * k1);
+    GX_TRY(call, hipMemcpyAsync(hp.data(), s.ph, hp.size() * sizeof(SrchHit), hipMemcpyDeviceToHost, call.st));
+    GX_TRY(call, hipStreamSynchronize(call.st));
+    candidates_only(hp.data(), npat, k1, hits);
+    return call.done(rc);
 }
 
 // Each pattern's (position, distance) pairs ascending by position (positions are distinct within a pattern).
@@ -273,24 +370,15 @@ void sort_pairs(uint32_t* positions, uint8_t* distances, const uint64_t* hit_off
 int approx_host(const gx_suffix_index* idx, const uint8_t* pats, const uint32_t* offs, size_t npat, uint32_t k,
                 gx_approx_hit* hits, uint32_t max_hits, uint32_t* positions, uint8_t* distances, size_t cap,
                 uint64_t* hit_offsets) {
-    const uint32_t n = (uint32_t)idx->n, N = n + 1, k1 = k + 1;
+    const uint32_t n = (uint32_t)idx->n, k1 = k + 1;
     const uint8_t* t = idx->text.data();
     const uint32_t* sa = idx->sa.data();
-    // seeds: every piece through the exact search, in candidate order
-    std::vector<SrchHit> ph(npat * k1);
-    uint64_t words = 0, total = 0;
-    for (size_t p = 0; p < npat; ++p) {
-        const uint32_t m = offs[p + 1] - offs[p];
-        for (uint32_t j = 0; j < k1; ++j) {
-            const uint32_t ps = aprx_piece_start(m, k1, j), pe = aprx_piece_start(m, k1, j + 1);
-            ph[p * k1 + j] = srch_one(t, sa, N, pats + offs[p] + ps, pe - ps, &words);
-            total += ph[p * k1 + j].count;
-        }
-    }
-    const uint64_t budget = approx_budget();
+    std::vector<SrchHit> ph;
+    uint64_t words = 0;
+    const uint64_t total = seed_pieces_host(idx, pats, offs, npat, k1, ph, &words), budget = approx_budget();
     if (total > budget) {
         candidates_only(ph.data(), npat, k1, hits);
-        return budget_error(total, budget);
+        return seed_budget_error("approximate search", total, budget);
     }
     std::vector<uint64_t> out;   // position << 8 | distance, the reported ones of every pattern in turn
     for (size_t p = 0; p < npat; ++p) {
@@ -340,129 +428,61 @@ int approx_device(gx_suffix_index* idx, const uint8_t* pats, size_t total_bytes,
     gx_context* ctx = idx->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
+    DevCall call(ctx);
+    hipStream_t st = call.st;
     const uint32_t N = (uint32_t)idx->n + 1, k1 = k + 1, npieces = npat * k1;
     ctx->aprx_cands = ctx->aprx_words = 0;
     ctx->aprx_seed_ms = ctx->aprx_verify_ms = 0.0;
-    DevBuf d_pat, d_off, d_poff, d_phits, d_coff, d_tmp, d_small, d_keep, d_ktmp, d_dist, d_start, d_best, d_hits, d_oq,
-        d_pos, d_dst;
-    auto done = [&](int rc) {
-        if (rc != GX_OK) (void)hipStreamSynchronize(st);   // nothing of this call still runs on the buffers
-        for (DevBuf* b : {&d_pat, &d_off, &d_poff, &d_phits, &d_coff, &d_tmp, &d_small, &d_keep, &d_ktmp, &d_dist,
-                          &d_start, &d_best, &d_hits, &d_oq, &d_pos, &d_dst})
-            pool_put(ctx, *b);
-        return rc;
-    };
-#define SR_TRY(expr)                                                                                          \
-    do {                                                                                                      \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess)                                                                                 \
-            return done(fail(e_ == hipErrorOutOfMemory ? GX_ENOMEM : GX_EHIP,                                 \
-                             std::string(#expr) + ": " + hipGetErrorString(e_)));                             \
-    } while (0)
-#define SR_GET(buf, bytes)                                                      \
-    do {                                                                        \
-        const int rc_ = pool_get(ctx, (bytes), &(buf), st);                     \
-        if (rc_ != GX_OK) return done(rc_);                                     \
-    } while (0)
-    // patterns and offsets as the exact search stages them; the piece offsets are the device's own
-    SR_GET(d_pat, total_bytes + kSufPad);
-    SR_GET(d_off, ((size_t)npat + 1) * 4);
-    SR_GET(d_poff, ((size_t)npieces + 1) * 4);
-    SR_GET(d_phits, (size_t)npieces * sizeof(SrchHit));
-    SR_GET(d_coff, ((size_t)npieces + 1) * 4);
-    SR_GET(d_tmp, suf_tiles((size_t)npieces + 1) * 4);
-    SR_GET(d_small, 64);
-    unsigned long long* d_cnt = (unsigned long long*)d_small.p;   // [0] seed word steps, [1] seed hits, [2] verify word steps
-    SR_TRY(hipMemcpyAsync(d_pat.p, pats, total_bytes, hipMemcpyHostToDevice, st));
-    SR_TRY(hipMemsetAsync((uint8_t*)d_pat.p + total_bytes, 0, kSufPad, st));
-    SR_TRY(hipMemcpyAsync(d_off.p, offs, ((size_t)npat + 1) * 4, hipMemcpyHostToDevice, st));
-    SR_TRY(hipMemsetAsync(d_cnt, 0, 24, st));
+    // patterns and offsets as the exact search stages them; counters: [0] seed word steps, [1] seed hits,
+    // [2] verify word steps
+    StagedBatch b;
+    if (const int rc = stage_batch(call, "approximate search", pats, total_bytes, offs, npat, b)) return rc;
+    DevSeeds s;
+    if (const int rc = seed_pieces_device(call, idx, b, npat, k1, &ctx->aprx_seed_ms, s)) return rc;
+    const uint64_t total = s.total, budget = approx_budget();
+    ctx->aprx_cands = total;
+    if (total > budget) return refuse_device(call, s, npat, k1, hits, seed_budget_error("approximate search", total, budget));
+    // stages 5 and 6: verify, compact
     const uint8_t* text = (const uint8_t*)idx->d_text.p;
     const uint32_t* sa = (const uint32_t*)idx->d_sa.p;
-    const uint8_t* dp = (const uint8_t*)d_pat.p;
-    const uint32_t* off = (const uint32_t*)d_off.p;
-    uint32_t* poff = (uint32_t*)d_poff.p;
-    SrchHit* ph = (SrchHit*)d_phits.p;
-    uint32_t* coff = (uint32_t*)d_coff.p;
-    // stages 1 to 4: pieces, seeds, their 64-bit total, candidate offsets.  The scan is 32-bit and is
-    // relied upon only once the host has held the total against the budget.
-    SR_TRY(hipEventRecord(ctx->ev0, st));
-    SR_TRY(launch_aprx_pieces(off, npat, k1, poff, st));
-    SR_TRY(launch_srch_range(text, sa, N, dp, poff, npieces, ph, d_cnt, st));
-    SR_TRY(launch_aprx_total(ph, npieces, d_cnt + 1, st));
-    SR_TRY(launch_srch_clamp(ph, npieces, 0xFFFFFFFFu, coff, st));
-    SR_TRY(launch_suf_scan(coff, npieces + 1, false, (uint32_t*)d_tmp.p, st));
-    SR_TRY(hipEventRecord(ctx->ev1, st));
-    unsigned long long* pin = (unsigned long long*)io_pinned(ctx, 128);
-    if (!pin) return done(fail(GX_ENOMEM, "approximate search: pinned staging"));
-    SR_TRY(hipMemcpyAsync(pin, d_cnt, 16, hipMemcpyDeviceToHost, st));
-    SR_TRY(hipStreamSynchronize(st));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) ctx->aprx_seed_ms = ms;
-    const uint64_t total = pin[1], budget = approx_budget();
-    ctx->aprx_cands = total;
-    if (total > budget) {
-        std::vector<SrchHit> hp(npieces);
-        SR_TRY(hipMemcpyAsync(hp.data(), ph, (size_t)npieces * sizeof(SrchHit), hipMemcpyDeviceToHost, st));
-        SR_TRY(hipStreamSynchronize(st));
-        candidates_only(hp.data(), npat, k1, hits);
-        return done(budget_error(total, budget));
-    }
-    // stages 5 and 6: verify, compact
     const uint32_t T = (uint32_t)total;   // <= 2^31
     const uint64_t dev_cap =
         positions ? std::min<uint64_t>(std::min<uint64_t>(cap, total), (uint64_t)npat * std::min(max_hits, N)) : 0;
-    SR_GET(d_keep, ((size_t)T + 1) * 4);
-    SR_GET(d_ktmp, suf_tiles((size_t)T + 1) * 4);
-    SR_GET(d_dist, std::max<size_t>(T, 1));
-    SR_GET(d_start, std::max<size_t>(T, 1) * 4);
-    SR_GET(d_best, (size_t)npat * 8);
-    SR_GET(d_hits, (size_t)npat * sizeof(AprxHit));
-    SR_GET(d_oq, ((size_t)npat + 1) * 4);
+    uint32_t *keep = nullptr, *ktmp = nullptr, *start = nullptr, *oq = nullptr, *d_pos = nullptr;
+    uint8_t *dist = nullptr, *d_dst = nullptr;
+    unsigned long long* best = nullptr;
+    AprxHit* d_hits = nullptr;
+    GX_GET(call, keep, (size_t)T + 1);
+    GX_GET(call, ktmp, suf_tiles((size_t)T + 1));
+    GX_GET(call, dist, std::max<size_t>(T, 1));
+    GX_GET(call, start, std::max<size_t>(T, 1));
+    GX_GET(call, best, npat);
+    GX_GET(call, d_hits, npat);
+    GX_GET(call, oq, (size_t)npat + 1);
     if (dev_cap) {
-        SR_GET(d_pos, (size_t)dev_cap * 4);
-        SR_GET(d_dst, (size_t)dev_cap);
+        GX_GET(call, d_pos, (size_t)dev_cap);
+        GX_GET(call, d_dst, (size_t)dev_cap);
     }
-    uint32_t* keep = (uint32_t*)d_keep.p;
-    uint32_t* oq = (uint32_t*)d_oq.p;
-    SR_TRY(hipMemsetAsync(d_best.p, 0xFF, (size_t)npat * 8, st));
-    SR_TRY(hipEventRecord(ctx->ev1, st));
-    SR_TRY(launch_aprx_verify(text, sa, N, dp, off, poff, ph, coff, npieces, k, T, keep, (uint8_t*)d_dist.p,
-                              (uint32_t*)d_start.p, (unsigned long long*)d_best.p, d_cnt + 2, st));
-    SR_TRY(launch_suf_scan(keep, T + 1, false, (uint32_t*)d_ktmp.p, st));
-    SR_TRY(launch_aprx_fill(coff, keep, (const unsigned long long*)d_best.p, npat, k1, max_hits, (AprxHit*)d_hits.p, oq,
-                            st));
+    GX_TRY(call, hipMemsetAsync(best, 0xFF, (size_t)npat * 8, st));
+    GX_TRY(call, hipEventRecord(ctx->ev1, st));
+    GX_TRY(call, launch_aprx_verify(text, sa, N, b.bytes, b.off, s.poff, s.ph, s.coff, npieces, k, T, keep, dist, start, best,
+                                    b.cnt + 2, st));
+    GX_TRY(call, launch_suf_scan(keep, T + 1, false, ktmp, st));
+    GX_TRY(call, launch_aprx_fill(s.coff, keep, best, npat, k1, max_hits, d_hits, oq, st));
     if (dev_cap) {
-        SR_TRY(launch_suf_scan(oq, npat + 1, false, (uint32_t*)d_tmp.p, st));
-        SR_TRY(launch_aprx_scatter(coff, keep, oq, npat, k1, T, max_hits, (const uint32_t*)d_start.p,
-                                   (const uint8_t*)d_dist.p, (uint32_t*)d_pos.p, (uint8_t*)d_dst.p, dev_cap, st));
+        GX_TRY(call, launch_suf_scan(oq, npat + 1, false, s.tmp, st));
+        GX_TRY(call, launch_aprx_scatter(s.coff, keep, oq, npat, k1, T, max_hits, start, dist, d_pos, d_dst, dev_cap, st));
     }
-    SR_TRY(hipEventRecord(ctx->ev2, st));
+    GX_TRY(call, hipEventRecord(ctx->ev2, st));
     // (behind the last event: the events time kernels alone)
-    SR_TRY(hipMemcpyAsync(pin + 2, d_cnt + 2, 8, hipMemcpyDeviceToHost, st));
-    SR_TRY(hipMemcpyAsync(hits, d_hits.p, (size_t)npat * sizeof(AprxHit), hipMemcpyDeviceToHost, st));
-    SR_TRY(hipStreamSynchronize(st));
-    if (hipEventElapsedTime(&ms, ctx->ev1, ctx->ev2) == hipSuccess) ctx->aprx_verify_ms = ms;
-    ctx->aprx_words = pin[2];
-    if (!positions) {
-        if (hit_offsets) offsets_of(hits, npat, max_hits, hit_offsets);
-        return done(GX_OK);
-    }
-    // the positions: their number is known to the host only now, so that GX_ECAP leaves positions[] and
-    // distances[] untouched and the copies move no more than them (a total above dev_cap is above cap)
-    const uint64_t total_out = offsets_of(hits, npat, max_hits, hit_offsets);
-    if (total_out > cap) return done(cap_error(total_out, cap));
-    if (total_out) {
-        SR_TRY(hipMemcpyAsync(positions, d_pos.p, (size_t)total_out * 4, hipMemcpyDeviceToHost, st));
-        SR_TRY(hipMemcpyAsync(distances, d_dst.p, (size_t)total_out, hipMemcpyDeviceToHost, st));
-        SR_TRY(hipStreamSynchronize(st));
-    }
-    done(GX_OK);   // (the stream is idle)
-#undef SR_TRY
-#undef SR_GET
-    sort_pairs(positions, distances, hit_offsets, npat);
-    return GX_OK;
+    GX_TRY(call, hipMemcpyAsync(b.pin + 2, b.cnt + 2, 8, hipMemcpyDeviceToHost, st));
+    GX_TRY(call, hipMemcpyAsync(hits, d_hits, (size_t)npat * sizeof(AprxHit), hipMemcpyDeviceToHost, st));
+    GX_TRY(call, hipStreamSynchronize(st));
+    call.elapsed(ctx->ev1, ctx->ev2, &ctx->aprx_verify_ms);
+    ctx->aprx_words = b.pin[2];
+    const int rc = finish_hits(call, hits, npat, max_hits, false, cap, hit_offsets, {{positions, d_pos, 4}, {distances, d_dst, 1}});
+    if (rc == GX_OK && positions) sort_pairs(positions, distances, hit_offsets, npat);
+    return rc;
 }
 
 // ---------------------------------------------------------------------------
@@ -473,53 +493,25 @@ int approx_device(gx_suffix_index* idx, const uint8_t* pats, size_t total_bytes,
 static_assert(sizeof(gx_edit_hit) == sizeof(EditHit), "gx_edit_hit layout");
 static_assert(GX_EDIT_MAX_M == kEditMaxM, "GX_EDIT_MAX_M");
 
-int edit_seed_error(uint64_t total, uint64_t budget) {
-    return fail(GX_ERANGE, "edit search: " + std::to_string(total) + " seed hits, more than GX_APPROX_CAND_BUDGET = " +
-                               std::to_string(budget) + ": split the batch, lower k, or raise GX_APPROX_CAND_BUDGET");
-}
-
 int edit_ends_error(uint64_t total, uint64_t budget) {
     return fail(GX_ERANGE, "edit search: " + std::to_string(total) +
                                " reported ends before dedupe, more than GX_APPROX_CAND_BUDGET = " + std::to_string(budget) +
                                ": split the batch, lower k, or raise GX_APPROX_CAND_BUDGET");
 }
 
-void edit_candidates_only(const SrchHit* ph, size_t npat, uint32_t k1, gx_edit_hit* hits) {
-    for (size_t p = 0; p < npat; ++p) {
-        uint64_t c = 0;
-        for (uint32_t j = 0; j < k1; ++j) c += ph[p * k1 + j].count;
-        hits[p].candidates = (uint32_t)std::min<uint64_t>(c, 0xFFFFFFFFull);
-    }
-}
-
-// The radix passes that sort pattern << 32 | end: a key byte that is zero in
-// every key (ends <= n, patterns < npat) is skipped, as the suffix sort's masks
-// skip constant digits.
-bool edit_pass_needed(int p, uint32_t n, uint32_t npat) {
-    return p < 4 ? (n >> (8 * p)) != 0 : ((npat - 1) >> (8 * (p - 4))) != 0;
-}
-
 // pats: padded as for search_host.
 int edit_host(const gx_suffix_index* idx, const uint8_t* pats, const uint32_t* offs, size_t npat, uint32_t k,
               gx_edit_hit* hits, uint32_t max_hits, uint32_t* ends, uint8_t* distances, uint32_t* starts, size_t cap,
               uint64_t* hit_offsets) {
-    const uint32_t n = (uint32_t)idx->n, N = n + 1, k1 = k + 1;
+    const uint32_t n = (uint32_t)idx->n, k1 = k + 1;
     const uint8_t* t = idx->text.data();
     const uint32_t* sa = idx->sa.data();
-    std::vector<SrchHit> ph(npat * k1);
-    uint64_t words = 0, total = 0, cells = 0;
-    for (size_t p = 0; p < npat; ++p) {
-        const uint32_t m = offs[p + 1] - offs[p];
-        for (uint32_t j = 0; j < k1; ++j) {
-            const uint32_t ps = aprx_piece_start(m, k1, j), pe = aprx_piece_start(m, k1, j + 1);
-            ph[p * k1 + j] = srch_one(t, sa, N, pats + offs[p] + ps, pe - ps, &words);
-            total += ph[p * k1 + j].count;
-        }
-    }
-    const uint64_t budget = approx_budget();
+    std::vector<SrchHit> ph;
+    uint64_t words = 0, cells = 0;
+    const uint64_t total = seed_pieces_host(idx, pats, offs, npat, k1, ph, &words), budget = approx_budget();
     if (total > budget) {
-        edit_candidates_only(ph.data(), npat, k1, hits);
-        return edit_seed_error(total, budget);
+        candidates_only(ph.data(), npat, k1, hits);
+        return seed_budget_error("edit search", total, budget);
     }
     // verify: every reported (pattern << 32 | end, distance), in candidate order
     std::vector<std::pair<uint64_t, uint32_t>> rep;
@@ -539,7 +531,7 @@ int edit_host(const gx_suffix_index* idx, const uint8_t* pats, const uint32_t* o
                         rep.emplace_back((uint64_t)p << 32 | (uint32_t)((int64_t)m + d0 - k + sl), edit_slot_dist(mk, nb, sl));
                 if (rep.size() > budget) {
                     // (the device sums every candidate's ends before it refuses; the host stops at the first one over)
-                    edit_candidates_only(ph.data(), npat, k1, hits);
+                    candidates_only(ph.data(), npat, k1, hits);
                     return edit_ends_error(rep.size(), budget);
                 }
             }
@@ -598,168 +590,94 @@ int edit_device(gx_suffix_index* idx, const uint8_t* pats, size_t total_bytes, c
     gx_context* ctx = idx->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
-    hipStream_t st = ctx->stream;
+    DevCall call(ctx);
+    hipStream_t st = call.st;
     const uint32_t n = (uint32_t)idx->n, N = n + 1, k1 = k + 1, npieces = npat * k1;
     ctx->edit_cands = ctx->edit_ends = ctx->edit_cells = 0;
     ctx->edit_seed_ms = ctx->edit_verify_ms = ctx->edit_dedupe_ms = 0.0;
-    DevBuf d_pat, d_off, d_poff, d_phits, d_coff, d_tmp, d_small, d_ecnt, d_etmp, d_rep, d_nib, d_key[2], d_val[2], d_table,
-        d_stmp, d_head, d_best, d_hits, d_hbase, d_oq, d_pos, d_dst, d_sta;
-    auto done = [&](int rc) {
-        if (rc != GX_OK) (void)hipStreamSynchronize(st);   // nothing of this call still runs on the buffers
-        for (DevBuf* b : {&d_pat, &d_off, &d_poff, &d_phits, &d_coff, &d_tmp, &d_small, &d_ecnt, &d_etmp, &d_rep, &d_nib,
-                          &d_key[0], &d_key[1], &d_val[0], &d_val[1], &d_table, &d_stmp, &d_head, &d_best, &d_hits,
-                          &d_hbase, &d_oq, &d_pos, &d_dst, &d_sta})
-            pool_put(ctx, *b);
-        return rc;
-    };
-#define SR_TRY(expr)                                                                                          \
-    do {                                                                                                      \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess)                                                                                 \
-            return done(fail(e_ == hipErrorOutOfMemory ? GX_ENOMEM : GX_EHIP,                                 \
-                             std::string(#expr) + ": " + hipGetErrorString(e_)));                             \
-    } while (0)
-#define SR_GET(buf, bytes)                                                      \
-    do {                                                                        \
-        const int rc_ = pool_get(ctx, (bytes), &(buf), st);                     \
-        if (rc_ != GX_OK) return done(rc_);                                     \
-    } while (0)
-    SR_GET(d_pat, total_bytes + kSufPad);
-    SR_GET(d_off, ((size_t)npat + 1) * 4);
-    SR_GET(d_poff, ((size_t)npieces + 1) * 4);
-    SR_GET(d_phits, (size_t)npieces * sizeof(SrchHit));
-    SR_GET(d_coff, ((size_t)npieces + 1) * 4);
-    SR_GET(d_tmp, suf_tiles((size_t)npieces + 1) * 4);
-    SR_GET(d_small, 64);
-    unsigned long long* d_cnt = (unsigned long long*)d_small.p;   // [0] seed word steps, [1] seed hits, [2] ends before dedupe, [3] cell updates
-    SR_TRY(hipMemcpyAsync(d_pat.p, pats, total_bytes, hipMemcpyHostToDevice, st));
-    SR_TRY(hipMemsetAsync((uint8_t*)d_pat.p + total_bytes, 0, kSufPad, st));
-    SR_TRY(hipMemcpyAsync(d_off.p, offs, ((size_t)npat + 1) * 4, hipMemcpyHostToDevice, st));
-    SR_TRY(hipMemsetAsync(d_cnt, 0, 32, st));
-    const uint8_t* text = (const uint8_t*)idx->d_text.p;
-    const uint32_t* sa = (const uint32_t*)idx->d_sa.p;
-    const uint8_t* dp = (const uint8_t*)d_pat.p;
-    const uint32_t* off = (const uint32_t*)d_off.p;
-    uint32_t* poff = (uint32_t*)d_poff.p;
-    SrchHit* ph = (SrchHit*)d_phits.p;
-    uint32_t* coff = (uint32_t*)d_coff.p;
+    // counters: [0] seed word steps, [1] seed hits, [2] ends before dedupe, [3] cell updates
+    StagedBatch b;
+    if (const int rc = stage_batch(call, "edit search", pats, total_bytes, offs, npat, b)) return rc;
     // pieces, seeds, their 64-bit total, candidate offsets: DESIGN.md 19.2 stages 1 to 4
-    SR_TRY(hipEventRecord(ctx->ev0, st));
-    SR_TRY(launch_aprx_pieces(off, npat, k1, poff, st));
-    SR_TRY(launch_srch_range(text, sa, N, dp, poff, npieces, ph, d_cnt, st));
-    SR_TRY(launch_aprx_total(ph, npieces, d_cnt + 1, st));
-    SR_TRY(launch_srch_clamp(ph, npieces, 0xFFFFFFFFu, coff, st));
-    SR_TRY(launch_suf_scan(coff, npieces + 1, false, (uint32_t*)d_tmp.p, st));
-    SR_TRY(hipEventRecord(ctx->ev1, st));
-    unsigned long long* pin = (unsigned long long*)io_pinned(ctx, 128);
-    if (!pin) return done(fail(GX_ENOMEM, "edit search: pinned staging"));
-    SR_TRY(hipMemcpyAsync(pin, d_cnt, 16, hipMemcpyDeviceToHost, st));
-    SR_TRY(hipStreamSynchronize(st));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) ctx->edit_seed_ms = ms;
-    const uint64_t total = pin[1], budget = approx_budget();
+    DevSeeds s;
+    if (const int rc = seed_pieces_device(call, idx, b, npat, k1, &ctx->edit_seed_ms, s)) return rc;
+    const uint64_t total = s.total, budget = approx_budget();
     ctx->edit_cands = total;
-    std::vector<SrchHit> hp;   // the refusals' only output comes from the pieces' intervals
-    auto refuse = [&](int rc) {
-        hp.resize(npieces);
-        if (hipMemcpyAsync(hp.data(), ph, (size_t)npieces * sizeof(SrchHit), hipMemcpyDeviceToHost, st) == hipSuccess &&
-            hipStreamSynchronize(st) == hipSuccess)
-            edit_candidates_only(hp.data(), npat, k1, hits);
-        return done(rc);
-    };
-    if (total > budget) return refuse(edit_seed_error(total, budget));
+    if (total > budget) return refuse_device(call, s, npat, k1, hits, seed_budget_error("edit search", total, budget));
     // the band on every candidate; what it reports is summed in 64 bits and held against the budget
     // before the 32-bit scan of the numbers is relied upon
+    const uint8_t* text = (const uint8_t*)idx->d_text.p;
+    const uint32_t* sa = (const uint32_t*)idx->d_sa.p;
     const uint32_t T = (uint32_t)total;   // <= 2^31
-    SR_GET(d_ecnt, ((size_t)T + 1) * 4);
-    SR_GET(d_etmp, suf_tiles((size_t)T + 1) * 4);
-    SR_GET(d_rep, std::max<size_t>(T, 1) * 4);
-    SR_GET(d_nib, std::max<size_t>(T, 1) * 8);
-    uint32_t* ecnt = (uint32_t*)d_ecnt.p;
-    SR_TRY(hipEventRecord(ctx->ev1, st));
-    SR_TRY(launch_edit_verify(text, sa, N, dp, off, poff, ph, coff, npieces, k, T, ecnt, (uint32_t*)d_rep.p,
-                              (uint64_t*)d_nib.p, d_cnt + 2, d_cnt + 3, st));
-    SR_TRY(hipEventRecord(ctx->ev2, st));
-    SR_TRY(hipMemcpyAsync(pin + 2, d_cnt + 2, 16, hipMemcpyDeviceToHost, st));
-    SR_TRY(hipStreamSynchronize(st));
-    if (hipEventElapsedTime(&ms, ctx->ev1, ctx->ev2) == hipSuccess) ctx->edit_verify_ms = ms;
-    ctx->edit_ends = pin[2];
-    ctx->edit_cells = pin[3];
-    if (pin[2] > budget) return refuse(edit_ends_error(pin[2], budget));
+    uint32_t *ecnt = nullptr, *etmp = nullptr, *rep = nullptr;
+    uint64_t* nib = nullptr;
+    GX_GET(call, ecnt, (size_t)T + 1);
+    GX_GET(call, etmp, suf_tiles((size_t)T + 1));
+    GX_GET(call, rep, std::max<size_t>(T, 1));
+    GX_GET(call, nib, std::max<size_t>(T, 1));
+    GX_TRY(call, hipEventRecord(ctx->ev1, st));
+    GX_TRY(call, launch_edit_verify(text, sa, N, b.bytes, b.off, s.poff, s.ph, s.coff, npieces, k, T, ecnt, rep, nib, b.cnt + 2,
+                                    b.cnt + 3, st));
+    GX_TRY(call, hipEventRecord(ctx->ev2, st));
+    GX_TRY(call, hipMemcpyAsync(b.pin + 2, b.cnt + 2, 16, hipMemcpyDeviceToHost, st));
+    GX_TRY(call, hipStreamSynchronize(st));
+    call.elapsed(ctx->ev1, ctx->ev2, &ctx->edit_verify_ms);
+    ctx->edit_ends = b.pin[2];
+    ctx->edit_cells = b.pin[3];
+    if (b.pin[2] > budget) return refuse_device(call, s, npat, k1, hits, edit_ends_error(b.pin[2], budget));
     // dedupe: scan, emit, sort, heads, scan, fill, scan, scatter; then the starts
-    const uint32_t E = (uint32_t)pin[2];   // <= 2^31
+    const uint32_t E = (uint32_t)b.pin[2];   // <= 2^31
     const size_t tiles = suf_tiles(E), table_n = 256 * tiles;
     const uint64_t dev_cap =
         ends ? std::min<uint64_t>(std::min<uint64_t>(cap, E), (uint64_t)npat * std::min(max_hits, N)) : 0;
+    uint64_t* key[2] = {nullptr, nullptr};
+    uint32_t* val[2] = {nullptr, nullptr};
+    uint32_t *table = nullptr, *stmp = nullptr, *head = nullptr, *hbase = nullptr, *oq = nullptr, *d_pos = nullptr,
+             *d_sta = nullptr;
+    uint8_t* d_dst = nullptr;
+    unsigned long long* best = nullptr;
+    EditHit* d_hits = nullptr;
     for (int q = 0; q < 2; ++q) {
-        SR_GET(d_key[q], std::max<size_t>(E, 1) * 8);
-        SR_GET(d_val[q], std::max<size_t>(E, 1) * 4);
+        GX_GET(call, key[q], std::max<size_t>(E, 1));
+        GX_GET(call, val[q], std::max<size_t>(E, 1));
     }
-    SR_GET(d_table, std::max<size_t>(table_n, 1) * 4);
-    SR_GET(d_stmp, std::max<size_t>(std::max(suf_tiles(table_n), suf_tiles((size_t)E + 1)), 1) * 4);
-    SR_GET(d_head, ((size_t)E + 1) * 4);
-    SR_GET(d_best, (size_t)npat * 8);
-    SR_GET(d_hits, (size_t)npat * sizeof(EditHit));
-    SR_GET(d_hbase, (size_t)npat * 4);
-    SR_GET(d_oq, ((size_t)npat + 1) * 4);
+    GX_GET(call, table, std::max<size_t>(table_n, 1));
+    GX_GET(call, stmp, std::max<size_t>(std::max(suf_tiles(table_n), suf_tiles((size_t)E + 1)), 1));
+    GX_GET(call, head, (size_t)E + 1);
+    GX_GET(call, best, npat);
+    GX_GET(call, d_hits, npat);
+    GX_GET(call, hbase, npat);
+    GX_GET(call, oq, (size_t)npat + 1);
     if (dev_cap) {
-        SR_GET(d_pos, (size_t)dev_cap * 4);
-        SR_GET(d_dst, (size_t)dev_cap);
-        if (starts) SR_GET(d_sta, (size_t)dev_cap * 4);
+        GX_GET(call, d_pos, (size_t)dev_cap);
+        GX_GET(call, d_dst, (size_t)dev_cap);
+        if (starts) GX_GET(call, d_sta, (size_t)dev_cap);
     }
     int cur = 0;
-    auto K = [&](int q) { return (uint64_t*)d_key[q].p; };
-    auto V = [&](int q) { return (uint32_t*)d_val[q].p; };
-    uint32_t* head = (uint32_t*)d_head.p;
-    uint32_t* oq = (uint32_t*)d_oq.p;
-    SR_TRY(hipMemsetAsync(d_best.p, 0xFF, (size_t)npat * 8, st));
-    SR_TRY(hipEventRecord(ctx->ev1, st));
+    GX_TRY(call, hipMemsetAsync(best, 0xFF, (size_t)npat * 8, st));
+    GX_TRY(call, hipEventRecord(ctx->ev1, st));
     if (E) {
-        SR_TRY(launch_suf_scan(ecnt, T + 1, false, (uint32_t*)d_etmp.p, st));
-        SR_TRY(launch_edit_emit(sa, N, off, poff, ph, coff, npieces, k, T, ecnt, (const uint32_t*)d_rep.p,
-                                (const uint64_t*)d_nib.p, K(cur), V(cur), st));
-        for (int p = 0; p < 8; ++p) {
-            if (!edit_pass_needed(p, n, npat)) continue;
-            SR_TRY(launch_suf_sort_pass(K(cur), V(cur), K(cur ^ 1), V(cur ^ 1), E, 8 * p, (uint32_t*)d_table.p,
-                                        (uint32_t*)d_stmp.p, st));
-            cur ^= 1;
-        }
+        GX_TRY(call, launch_suf_scan(ecnt, T + 1, false, etmp, st));
+        GX_TRY(call, launch_edit_emit(sa, N, b.off, s.poff, s.ph, s.coff, npieces, k, T, ecnt, rep, nib, key[0], val[0], st));
+        // the keys are pattern << 32 | end: ends <= n, patterns < npat
+        GX_TRY(call, radix_sort_pairs(key, val, E, table, stmp, radix_digits(n, npat - 1), st, &cur));
     }
-    uint32_t* dmin = V(cur ^ 1);   // (the sort's other buffer is free now)
-    SR_TRY(launch_edit_heads(K(cur), V(cur), E, k, head, dmin, (unsigned long long*)d_best.p, st));
-    SR_TRY(launch_suf_scan(head, E + 1, false, (uint32_t*)d_stmp.p, st));
-    SR_TRY(launch_edit_fill(K(cur), head, E, coff, (const unsigned long long*)d_best.p, npat, k1, max_hits,
-                            (EditHit*)d_hits.p, (uint32_t*)d_hbase.p, oq, st));
+    uint32_t* dmin = val[cur ^ 1];   // (the sort's other buffer is free now)
+    GX_TRY(call, launch_edit_heads(key[cur], val[cur], E, k, head, dmin, best, st));
+    GX_TRY(call, launch_suf_scan(head, E + 1, false, stmp, st));
+    GX_TRY(call, launch_edit_fill(key[cur], head, E, s.coff, best, npat, k1, max_hits, d_hits, hbase, oq, st));
     if (dev_cap) {
-        SR_TRY(launch_suf_scan(oq, npat + 1, false, (uint32_t*)d_tmp.p, st));
-        SR_TRY(launch_edit_scatter(K(cur), dmin, head, E, (const uint32_t*)d_hbase.p, oq, npat, max_hits,
-                                   (uint32_t*)d_pos.p, (uint8_t*)d_dst.p, dev_cap, st));
-        if (starts)
-            SR_TRY(launch_edit_starts(text, dp, off, oq, npat, k, (const uint32_t*)d_pos.p, (const uint8_t*)d_dst.p,
-                                      (uint32_t*)d_sta.p, dev_cap, st));
+        GX_TRY(call, launch_suf_scan(oq, npat + 1, false, s.tmp, st));
+        GX_TRY(call, launch_edit_scatter(key[cur], dmin, head, E, hbase, oq, npat, max_hits, d_pos, d_dst, dev_cap, st));
+        if (starts) GX_TRY(call, launch_edit_starts(text, b.bytes, b.off, oq, npat, k, d_pos, d_dst, d_sta, dev_cap, st));
     }
-    SR_TRY(hipEventRecord(ctx->ev2, st));
+    GX_TRY(call, hipEventRecord(ctx->ev2, st));
     // (behind the last event: the events time kernels alone)
-    SR_TRY(hipMemcpyAsync(hits, d_hits.p, (size_t)npat * sizeof(EditHit), hipMemcpyDeviceToHost, st));
-    SR_TRY(hipStreamSynchronize(st));
-    if (hipEventElapsedTime(&ms, ctx->ev1, ctx->ev2) == hipSuccess) ctx->edit_dedupe_ms = ms;
-    if (!ends) {
-        if (hit_offsets) offsets_of(hits, npat, max_hits, hit_offsets);
-        return done(GX_OK);
-    }
-    // the occurrences: their number is known to the host only now, so that GX_ECAP leaves the three arrays
-    // untouched and the copies move no more than them (a total above dev_cap is above cap)
-    const uint64_t total_out = offsets_of(hits, npat, max_hits, hit_offsets);
-    if (total_out > cap) return done(cap_error(total_out, cap));
-    if (total_out) {
-        SR_TRY(hipMemcpyAsync(ends, d_pos.p, (size_t)total_out * 4, hipMemcpyDeviceToHost, st));
-        SR_TRY(hipMemcpyAsync(distances, d_dst.p, (size_t)total_out, hipMemcpyDeviceToHost, st));
-        if (starts) SR_TRY(hipMemcpyAsync(starts, d_sta.p, (size_t)total_out * 4, hipMemcpyDeviceToHost, st));
-        SR_TRY(hipStreamSynchronize(st));
-    }
-#undef SR_TRY
-#undef SR_GET
-    return done(GX_OK);   // (the stream is idle)
+    GX_TRY(call, hipMemcpyAsync(hits, d_hits, (size_t)npat * sizeof(EditHit), hipMemcpyDeviceToHost, st));
+    GX_TRY(call, hipStreamSynchronize(st));
+    call.elapsed(ctx->ev1, ctx->ev2, &ctx->edit_dedupe_ms);
+    return finish_hits(call, hits, npat, max_hits, false, cap, hit_offsets,
+                       {{ends, d_pos, 4}, {distances, d_dst, 1}, {starts, d_sta, 4}});
 }
 
 }  // namespace
@@ -861,29 +779,75 @@ extern "C" int gx_suffix_index_export(const gx_suffix_index* idx, uint32_t* sa) 
     return GX_OK;
 }
 
-extern "C" int gx_suffix_index_search(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets, size_t npat,
-                                      gx_search_hit* hits, uint32_t max_hits, uint32_t* positions, size_t positions_cap,
-                                      uint64_t* hit_offsets) {
+namespace {
+
+// What the three searches' entry points differ in before a pattern byte is staged.
+struct SearchKind {
+    const char* what;    // its name in the messages; NULL: the exact search, which has no k
+    const char* out;     // its first output array
+    const char* every;   // what would match were a piece empty
+    uint32_t max_m;      // a pattern's most bytes where that is below the batch checker's (0: it is not)
+};
+constexpr SearchKind kExact{nullptr, "positions", nullptr, 0};
+constexpr SearchKind kApprox{"approximate search", "positions", "window", 0};
+constexpr SearchKind kEdit{"edit search", "ends", "end", kEditMaxM};
+
+// The checks of an entry point in their order, then the batch as the drivers take it.  *run: there is a
+// pattern to search for (without one hit_offsets[0] = 0 is the whole answer).
+int search_prologue(const SearchKind& kind, const gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets,
+                    size_t npat, uint32_t k, const void* hits, const void* out, const void* distances, const void* starts,
+                    uint64_t* hit_offsets, HostBatch& b, bool* run) {
+    *run = false;
     if (!idx) return fail(GX_EINVAL, "idx is NULL");
     if (!offsets) return fail(GX_EINVAL, "offsets is NULL");
     if (npat && !hits) return fail(GX_EINVAL, "hits is NULL");
-    if (positions && !hit_offsets) return fail(GX_EINVAL, "hit_offsets is NULL with positions");
-    const int brc = check_batch(patterns, offsets, npat);
+    if (out && !hit_offsets) return fail(GX_EINVAL, std::string("hit_offsets is NULL with ") + kind.out);
+    if (kind.what) {
+        if (out && !distances) return fail(GX_EINVAL, std::string("distances is NULL with ") + kind.out);
+        if (starts && !out) return fail(GX_EINVAL, "starts without ends");
+        if (k > kAprxMaxK) return fail(GX_EINVAL, "k is " + std::to_string(k) + ", more than GX_APPROX_MAX_K = 8");
+    }
+    const int brc = check_batch(kPatterns, patterns, offsets, npat);
     if (brc != GX_OK) return brc;
-    const uint64_t total_bytes = offsets[npat];
+    if (kind.what) {
+        for (size_t p = 0; p < npat; ++p) {
+            const uint64_t m = offsets[p + 1] - offsets[p];
+            if (m < (uint64_t)k + 1)
+                return fail(GX_EINVAL, "pattern " + std::to_string(p) + " has " + std::to_string(m) +
+                                           " bytes, fewer than k + 1 = " + std::to_string(k + 1) +
+                                           ": a piece would be empty and every " + kind.every + " would match");
+            if (kind.max_m && m > kind.max_m)
+                return fail(GX_ERANGE, "pattern " + std::to_string(p) + " has " + std::to_string(m) +
+                                           " bytes, more than GX_EDIT_MAX_M = " + std::to_string(kind.max_m));
+        }
+        // (the pieces are the interval kernel's patterns: their count plus one, and the scan's tile rounding, in 32 bits)
+        const uint64_t npieces = (uint64_t)npat * (k + 1);
+        if (npieces + 1 + kSufTile >= (1ull << 32))
+            return fail(GX_ERANGE, std::string(kind.what) + ": " + std::to_string(npieces) +
+                                       " pieces (npat * (k + 1)), 2^32 or more with the scan's rounding: split the batch");
+    }
     if (npat == 0) {
         if (hit_offsets) hit_offsets[0] = 0;
         return GX_OK;
     }
-    std::vector<uint32_t> offs(npat + 1);
-    for (size_t p = 0; p <= npat; ++p) offs[p] = (uint32_t)offsets[p];
+    narrow_batch(idx, patterns, offsets, npat, b);
+    *run = true;
+    return GX_OK;
+}
+
+}  // namespace
+
+extern "C" int gx_suffix_index_search(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets, size_t npat,
+                                      gx_search_hit* hits, uint32_t max_hits, uint32_t* positions, size_t positions_cap,
+                                      uint64_t* hit_offsets) {
+    HostBatch b;
+    bool run;
+    const int rc = search_prologue(kExact, idx, patterns, offsets, npat, 0, hits, positions, nullptr, nullptr, hit_offsets, b, &run);
+    if (!run) return rc;
     if (idx->ctx)
-        return search_device(idx, patterns, (size_t)total_bytes, offs.data(), (uint32_t)npat, hits, max_hits, positions,
+        return search_device(idx, patterns, (size_t)offsets[npat], b.offs.data(), (uint32_t)npat, hits, max_hits, positions,
                              positions_cap, hit_offsets);
-    // the host compares read 8 bytes at a time too: the same padding behind the patterns
-    std::vector<uint8_t> padded(total_bytes + kSufPad, 0);
-    if (total_bytes) memcpy(padded.data(), patterns, total_bytes);
-    return search_host(idx, padded.data(), offs.data(), npat, hits, max_hits, positions, positions_cap, hit_offsets);
+    return search_host(idx, b.padded.data(), b.offs.data(), npat, hits, max_hits, positions, positions_cap, hit_offsets);
 }
 
 extern "C" int gx_search_info(const gx_context* ctx, uint64_t* word_compares, double* search_ms, double* locate_ms) {
@@ -898,37 +862,14 @@ extern "C" int gx_suffix_index_search_approx(gx_suffix_index* idx, const uint8_t
                                              size_t npat, uint32_t k, gx_approx_hit* hits, uint32_t max_hits,
                                              uint32_t* positions, uint8_t* distances, size_t positions_cap,
                                              uint64_t* hit_offsets) {
-    if (!idx) return fail(GX_EINVAL, "idx is NULL");
-    if (!offsets) return fail(GX_EINVAL, "offsets is NULL");
-    if (npat && !hits) return fail(GX_EINVAL, "hits is NULL");
-    if (positions && !hit_offsets) return fail(GX_EINVAL, "hit_offsets is NULL with positions");
-    if (positions && !distances) return fail(GX_EINVAL, "distances is NULL with positions");
-    if (k > kAprxMaxK) return fail(GX_EINVAL, "k is " + std::to_string(k) + ", more than GX_APPROX_MAX_K = 8");
-    const int brc = check_batch(patterns, offsets, npat);
-    if (brc != GX_OK) return brc;
-    for (size_t p = 0; p < npat; ++p)
-        if (offsets[p + 1] - offsets[p] < (uint64_t)k + 1)
-            return fail(GX_EINVAL, "pattern " + std::to_string(p) + " has " + std::to_string(offsets[p + 1] - offsets[p]) +
-                                       " bytes, fewer than k + 1 = " + std::to_string(k + 1) +
-                                       ": a piece would be empty and every window would match");
-    // (the pieces are the interval kernel's patterns: their count plus one, and the scan's tile rounding, in 32 bits)
-    const uint64_t npieces = (uint64_t)npat * (k + 1);
-    if (npieces + 1 + kSufTile >= (1ull << 32))
-        return fail(GX_ERANGE, "approximate search: " + std::to_string(npieces) +
-                                   " pieces (npat * (k + 1)), 2^32 or more with the scan's rounding: split the batch");
-    const uint64_t total_bytes = offsets[npat];
-    if (npat == 0) {
-        if (hit_offsets) hit_offsets[0] = 0;
-        return GX_OK;
-    }
-    std::vector<uint32_t> offs(npat + 1);
-    for (size_t p = 0; p <= npat; ++p) offs[p] = (uint32_t)offsets[p];
+    HostBatch b;
+    bool run;
+    const int rc = search_prologue(kApprox, idx, patterns, offsets, npat, k, hits, positions, distances, nullptr, hit_offsets, b, &run);
+    if (!run) return rc;
     if (idx->ctx)
-        return approx_device(idx, patterns, (size_t)total_bytes, offs.data(), (uint32_t)npat, k, hits, max_hits, positions,
+        return approx_device(idx, patterns, (size_t)offsets[npat], b.offs.data(), (uint32_t)npat, k, hits, max_hits, positions,
                              distances, positions_cap, hit_offsets);
-    std::vector<uint8_t> padded(total_bytes + kSufPad, 0);
-    memcpy(padded.data(), patterns, total_bytes);
-    return approx_host(idx, padded.data(), offs.data(), npat, k, hits, max_hits, positions, distances, positions_cap,
+    return approx_host(idx, b.padded.data(), b.offs.data(), npat, k, hits, max_hits, positions, distances, positions_cap,
                        hit_offsets);
 }
 
@@ -946,42 +887,14 @@ extern "C" int gx_suffix_index_search_edit(gx_suffix_index* idx, const uint8_t* 
                                            size_t npat, uint32_t k, gx_edit_hit* hits, uint32_t max_hits, uint32_t* ends,
                                            uint8_t* distances, uint32_t* starts, size_t positions_cap,
                                            uint64_t* hit_offsets) {
-    if (!idx) return fail(GX_EINVAL, "idx is NULL");
-    if (!offsets) return fail(GX_EINVAL, "offsets is NULL");
-    if (npat && !hits) return fail(GX_EINVAL, "hits is NULL");
-    if (ends && !hit_offsets) return fail(GX_EINVAL, "hit_offsets is NULL with ends");
-    if (ends && !distances) return fail(GX_EINVAL, "distances is NULL with ends");
-    if (starts && !ends) return fail(GX_EINVAL, "starts without ends");
-    if (k > kAprxMaxK) return fail(GX_EINVAL, "k is " + std::to_string(k) + ", more than GX_APPROX_MAX_K = 8");
-    const int brc = check_batch(patterns, offsets, npat);
-    if (brc != GX_OK) return brc;
-    for (size_t p = 0; p < npat; ++p) {
-        const uint64_t m = offsets[p + 1] - offsets[p];
-        if (m < (uint64_t)k + 1)
-            return fail(GX_EINVAL, "pattern " + std::to_string(p) + " has " + std::to_string(m) +
-                                       " bytes, fewer than k + 1 = " + std::to_string(k + 1) +
-                                       ": a piece would be empty and every end would match");
-        if (m > kEditMaxM)
-            return fail(GX_ERANGE, "pattern " + std::to_string(p) + " has " + std::to_string(m) +
-                                       " bytes, more than GX_EDIT_MAX_M = 4096");
-    }
-    const uint64_t npieces = (uint64_t)npat * (k + 1);
-    if (npieces + 1 + kSufTile >= (1ull << 32))
-        return fail(GX_ERANGE, "edit search: " + std::to_string(npieces) +
-                                   " pieces (npat * (k + 1)), 2^32 or more with the scan's rounding: split the batch");
-    const uint64_t total_bytes = offsets[npat];
-    if (npat == 0) {
-        if (hit_offsets) hit_offsets[0] = 0;
-        return GX_OK;
-    }
-    std::vector<uint32_t> offs(npat + 1);
-    for (size_t p = 0; p <= npat; ++p) offs[p] = (uint32_t)offsets[p];
+    HostBatch b;
+    bool run;
+    const int rc = search_prologue(kEdit, idx, patterns, offsets, npat, k, hits, ends, distances, starts, hit_offsets, b, &run);
+    if (!run) return rc;
     if (idx->ctx)
-        return edit_device(idx, patterns, (size_t)total_bytes, offs.data(), (uint32_t)npat, k, hits, max_hits, ends,
+        return edit_device(idx, patterns, (size_t)offsets[npat], b.offs.data(), (uint32_t)npat, k, hits, max_hits, ends,
                            distances, starts, positions_cap, hit_offsets);
-    std::vector<uint8_t> padded(total_bytes + kSufPad, 0);
-    memcpy(padded.data(), patterns, total_bytes);
-    return edit_host(idx, padded.data(), offs.data(), npat, k, hits, max_hits, ends, distances, starts, positions_cap,
+    return edit_host(idx, b.padded.data(), b.offs.data(), npat, k, hits, max_hits, ends, distances, starts, positions_cap,
                      hit_offsets);
 }
 

@@ -16,8 +16,7 @@
 #include <charconv>
 #include <cmath>
 
-#include "gx_api.h"
-#include "gx_suffix.h"
+#include "gx_api_call.h"
 
 namespace {
 
@@ -138,20 +137,36 @@ void bwt_host(const uint8_t* t, const uint32_t* sa, size_t N, uint8_t* bwt) {
 // (GX_SUFFIX_LCP_BUDGET).  2^40 is about 130 times the A^(1 Mi) launch.
 constexpr uint64_t kSuffixLcpBudgetDefault = 1ull << 40;
 
+// The scope of a suffix-array construction, for GX_TRY and GX_GET as a DevCall (gx_api_call.h), over the
+// buffers of a SufDev, which outlive suffix_device_sa when it succeeds: done(GX_OK) leaves them with the
+// SufDev under `keep` and returns them otherwise; a failing done() waits until nothing of the call still runs
+// on them and returns them.
+struct SufCall {
+    gx_context* ctx;
+    SufDev& w;
+    bool keep;
+    int get(DevBuf& b, size_t bytes) { return pool_get(ctx, bytes, &b, ctx->stream); }
+    int done(int rc) {
+        if (rc != GX_OK) (void)hipStreamSynchronize(ctx->stream);
+        if (rc != GX_OK || !keep) w.release(ctx);
+        return rc;
+    }
+};
+
 }  // namespace
 
-#define SUF_TRY(expr)                                                                                         \
-    do {                                                                                                      \
-        hipError_t e_ = (expr);                                                                               \
-        if (e_ != hipSuccess)                                                                                 \
-            return done(fail(e_ == hipErrorOutOfMemory ? GX_ENOMEM : GX_EHIP,                                 \
-                             std::string(#expr) + ": " + hipGetErrorString(e_)));                             \
-    } while (0)
-#define SUF_GET(buf, bytes)                                                     \
-    do {                                                                        \
-        const int rc_ = pool_get(ctx, (bytes), &(buf), st);                     \
-        if (rc_ != GX_OK) return done(rc_);                                     \
-    } while (0)
+hipError_t radix_sort_pairs(uint64_t* const key[2], uint32_t* const val[2], uint32_t count, uint32_t* table, uint32_t* tmp,
+                            uint64_t digits, hipStream_t st, int* cur, unsigned* ran) {
+    for (int p = 0; p < 8; ++p) {
+        if (!((digits >> (8 * p)) & 0xffull)) continue;   // the same digit in every key
+        const int c = *cur;
+        const hipError_t e = launch_suf_sort_pass(key[c], val[c], key[c ^ 1], val[c ^ 1], count, 8 * p, table, tmp, st);
+        if (e != hipSuccess) return e;
+        *cur = c ^ 1;
+        if (ran) *ran |= 1u << p;
+    }
+    return hipSuccess;
+}
 
 // Text to device text and device suffix array (gx_api.h): what suffix-tree
 // mode and the suffix index (gx_api_search.cpp) share.
@@ -162,67 +177,61 @@ int suffix_device_sa(gx_context* ctx, const uint8_t* t, uint32_t N, bool with_st
     const size_t table_n = 256 * tiles;
     const size_t tmp_n = std::max(suf_tiles(table_n), tiles);
     const size_t nfb = (N + (size_t)kSufFoldBlock - 1) / kSufFoldBlock;
-    auto done = [&](int rc) {
-        if (rc != GX_OK) {
-            (void)hipStreamSynchronize(st);   // nothing of this call still runs on the buffers
-            w.release(ctx);
-        }
-        return rc;
-    };
-    SUF_GET(w.text, (size_t)N + kSufPad);
+    SufCall call{ctx, w, true};
+    GX_GET(call, w.text, (size_t)N + kSufPad);
     for (int q = 0; q < 2; ++q) {
-        SUF_GET(w.k[q], (size_t)N * 8);
-        SUF_GET(w.v[q], (size_t)N * 4);
+        GX_GET(call, w.k[q], (size_t)N * 8);
+        GX_GET(call, w.v[q], (size_t)N * 4);
     }
-    SUF_GET(w.rank, (size_t)N * 4);
-    SUF_GET(w.flags, (size_t)N * 4);
-    SUF_GET(w.table, table_n * 4);
-    SUF_GET(w.tmp, tmp_n * 4);
-    SUF_GET(w.small, 64);
-    if (with_stats) SUF_GET(w.fold, nfb * 28);
-    if (with_bwt) SUF_GET(w.bwt, (size_t)N);
+    GX_GET(call, w.rank, (size_t)N * 4);
+    GX_GET(call, w.flags, (size_t)N * 4);
+    GX_GET(call, w.table, table_n * 4);
+    GX_GET(call, w.tmp, tmp_n * 4);
+    GX_GET(call, w.small, 64);
+    if (with_stats) GX_GET(call, w.fold, nfb * 28);
+    if (with_bwt) GX_GET(call, w.bwt, (size_t)N);
     // device words: [0] OR of the keys, [1] their AND, [2] the last rank, [4..8) the fold
     uint64_t* d_masks = (uint64_t*)w.small.p;
     uint32_t* d_last = (uint32_t*)(d_masks + 2);
     // pinned words: [0..2) the masks' presets, [2..5) masks and last rank as read back, [8..12) the fold
     uint64_t* pin = w.pin = (uint64_t*)io_pinned(ctx, 128);
-    if (!pin) return done(fail(GX_ENOMEM, "suffix: pinned staging"));
+    if (!pin) return call.done(fail(GX_ENOMEM, "suffix: pinned staging"));
     pin[0] = 0;
     pin[1] = ~0ull;
     const uint8_t* text = (const uint8_t*)w.text.p;
     uint32_t* rank = (uint32_t*)w.rank.p;
     uint32_t* flags = (uint32_t*)w.flags.p;
     int cur = 0;
-    auto K = [&](int q) { return (uint64_t*)w.k[q].p; };
-    auto V = [&](int q) { return (uint32_t*)w.v[q].p; };
+    uint64_t* const K[2] = {(uint64_t*)w.k[0].p, (uint64_t*)w.k[1].p};
+    uint32_t* const V[2] = {(uint32_t*)w.v[0].p, (uint32_t*)w.v[1].p};
     // (a pageable source: the copy has left `t` once the stream is synchronised below)
-    SUF_TRY(hipMemcpyAsync(w.text.p, t, (size_t)N + kSufPad, hipMemcpyHostToDevice, st));
-    SUF_TRY(hipMemcpyAsync(d_masks, pin, 16, hipMemcpyHostToDevice, st));
-    SUF_TRY(launch_suf_keys0(text, N, K(cur), V(cur), d_masks, st));
-    SUF_TRY(hipMemcpyAsync(pin + 2, d_masks, 16, hipMemcpyDeviceToHost, st));
-    SUF_TRY(hipStreamSynchronize(st));
+    GX_TRY(call, hipMemcpyAsync(w.text.p, t, (size_t)N + kSufPad, hipMemcpyHostToDevice, st));
+    GX_TRY(call, hipMemcpyAsync(d_masks, pin, 16, hipMemcpyHostToDevice, st));
+    GX_TRY(call, launch_suf_keys0(text, N, K[cur], V[cur], d_masks, st));
+    GX_TRY(call, hipMemcpyAsync(pin + 2, d_masks, 16, hipMemcpyDeviceToHost, st));
+    GX_TRY(call, hipStreamSynchronize(st));
     uint64_t h = 8;   // after a round: suffixes with equal ranks agree in their first h bytes
     for (;; h *= 2) {
-        if (h >= (1ull << 31)) return done(fail(GX_EHIP, "suffix: the doubling did not converge"));
+        if (h >= (1ull << 31)) return call.done(fail(GX_EHIP, "suffix: the doubling did not converge"));
         const uint64_t diff = pin[2] ^ pin[3];   // bits in which the keys differ
-        SUF_TRY(hipEventRecord(ctx->ev0, st));
-        for (int p = 0; p < 8; ++p) {
-            if (!((diff >> (8 * p)) & 0xffull)) continue;   // the same digit in every key
-            SUF_TRY(launch_suf_sort_pass(K(cur), V(cur), K(cur ^ 1), V(cur ^ 1), N, 8 * p, (uint32_t*)w.table.p,
-                                         (uint32_t*)w.tmp.p, st));
-            cur ^= 1;
-            ++info.passes;
-            ++info.digit_passes[p];
-        }
-        SUF_TRY(hipEventRecord(ctx->ev1, st));
-        SUF_TRY(launch_suf_ranks(K(cur), V(cur), N, flags, (uint32_t*)w.tmp.p, rank, d_last, st));
+        GX_TRY(call, hipEventRecord(ctx->ev0, st));
+        unsigned ran = 0;
+        GX_TRY(call, radix_sort_pairs(K, V, N, (uint32_t*)w.table.p, (uint32_t*)w.tmp.p, diff, st, &cur, &ran));
+        for (int p = 0; p < 8; ++p)
+            if ((ran >> p) & 1u) {
+                ++info.passes;
+                ++info.digit_passes[p];
+            }
+        GX_TRY(call, hipEventRecord(ctx->ev1, st));
+        GX_TRY(call, launch_suf_ranks(K[cur], V[cur], N, flags, (uint32_t*)w.tmp.p, rank, d_last, st));
         // the next round's keys and masks ride along (unused when this round was the last)
-        SUF_TRY(hipMemcpyAsync(d_masks, pin, 16, hipMemcpyHostToDevice, st));
-        SUF_TRY(launch_suf_keys(rank, N, (uint32_t)h, K(cur ^ 1), V(cur ^ 1), d_masks, st));
-        SUF_TRY(hipMemcpyAsync(pin + 2, d_masks, 24, hipMemcpyDeviceToHost, st));
-        SUF_TRY(hipStreamSynchronize(st));
-        float ms = 0.f;
-        if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) info.sort_ms += ms;
+        GX_TRY(call, hipMemcpyAsync(d_masks, pin, 16, hipMemcpyHostToDevice, st));
+        GX_TRY(call, launch_suf_keys(rank, N, (uint32_t)h, K[cur ^ 1], V[cur ^ 1], d_masks, st));
+        GX_TRY(call, hipMemcpyAsync(pin + 2, d_masks, 24, hipMemcpyDeviceToHost, st));
+        GX_TRY(call, hipStreamSynchronize(st));
+        double ms = 0.0;
+        DevCall::elapsed(ctx->ev0, ctx->ev1, &ms);
+        info.sort_ms += ms;
         ++info.rounds;
         if ((uint32_t)pin[4] == N - 1) break;
         cur ^= 1;
@@ -244,11 +253,7 @@ int suffix_device(gx_context* ctx, const uint8_t* t, uint32_t N, gx_suffix_stats
         const int rc = suffix_device_sa(ctx, t, N, true, bwt != nullptr, w, info);
         if (rc != GX_OK) return rc;
     }
-    auto done = [&](int rc) {
-        if (rc != GX_OK) (void)hipStreamSynchronize(st);   // nothing of this call still runs on the buffers
-        w.release(ctx);
-        return rc;
-    };
+    SufCall call{ctx, w, false};
     DevBuf &d_fold = w.fold, &d_bwt = w.bwt;
     uint64_t* d_masks = (uint64_t*)w.small.p;
     SufFold* d_res = (SufFold*)(d_masks + 4);
@@ -262,9 +267,9 @@ int suffix_device(gx_context* ctx, const uint8_t* t, uint32_t N, gx_suffix_stats
     const uint64_t lanes = ((uint64_t)N + kSufLcpChunk - 1) / kSufLcpChunk;
     if (lanes * (h / 8) > suf_env_u64("GX_SUFFIX_LCP_BUDGET", kSuffixLcpBudgetDefault)) {
         std::vector<uint32_t> hsa(N), hrank(N), hlcp;
-        SUF_TRY(hipMemcpyAsync(hsa.data(), d_sa, (size_t)N * 4, hipMemcpyDeviceToHost, st));
-        SUF_TRY(hipStreamSynchronize(st));
-        done(GX_OK);   // (the stream is idle)
+        GX_TRY(call, hipMemcpyAsync(hsa.data(), d_sa, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+        GX_TRY(call, hipStreamSynchronize(st));
+        call.done(GX_OK);   // (the stream is idle)
         for (uint32_t k = 0; k < N; ++k) {
             if (hsa[k] >= N) return fail(GX_EHIP, "suffix: suffix array entry out of range");
             hrank[hsa[k]] = k;
@@ -277,25 +282,24 @@ int suffix_device(gx_context* ctx, const uint8_t* t, uint32_t N, gx_suffix_stats
         return GX_OK;   // (lcp_ms and fold_ms stay 0: those kernels did not run)
     }
     uint32_t* d_lcp = flags;   // (the head flags are done with)
-    if (bwt) SUF_TRY(launch_suf_bwt(text, d_sa, N, (uint8_t*)d_bwt.p, st));
-    SUF_TRY(hipEventRecord(ctx->ev0, st));
-    SUF_TRY(launch_suf_lcp(text, d_sa, rank, N, d_lcp, st));
-    SUF_TRY(hipEventRecord(ctx->ev1, st));
+    if (bwt) GX_TRY(call, launch_suf_bwt(text, d_sa, N, (uint8_t*)d_bwt.p, st));
+    GX_TRY(call, hipEventRecord(ctx->ev0, st));
+    GX_TRY(call, launch_suf_lcp(text, d_sa, rank, N, d_lcp, st));
+    GX_TRY(call, hipEventRecord(ctx->ev1, st));
     uint32_t* d_bmin = (uint32_t*)((uint8_t*)d_fold.p + nfb * 24);
     uint64_t* d_part = (uint64_t*)d_fold.p;
-    SUF_TRY(launch_suf_fold(d_lcp, d_sa, N, d_bmin, d_part, d_part + nfb, d_part + 2 * nfb, d_res, st));
-    SUF_TRY(hipEventRecord(ctx->ev2, st));
-    SUF_TRY(hipMemcpyAsync(pin + 8, d_res, sizeof(SufFold), hipMemcpyDeviceToHost, st));
-    if (bwt) SUF_TRY(hipMemcpyAsync(bwt, d_bwt.p, N, hipMemcpyDeviceToHost, st));
-    if (sa) SUF_TRY(hipMemcpyAsync(sa, d_sa, (size_t)N * 4, hipMemcpyDeviceToHost, st));
-    if (lcp) SUF_TRY(hipMemcpyAsync(lcp, d_lcp, (size_t)N * 4, hipMemcpyDeviceToHost, st));
-    SUF_TRY(hipStreamSynchronize(st));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) info.lcp_ms = ms;
-    if (hipEventElapsedTime(&ms, ctx->ev1, ctx->ev2) == hipSuccess) info.fold_ms = ms;
+    GX_TRY(call, launch_suf_fold(d_lcp, d_sa, N, d_bmin, d_part, d_part + nfb, d_part + 2 * nfb, d_res, st));
+    GX_TRY(call, hipEventRecord(ctx->ev2, st));
+    GX_TRY(call, hipMemcpyAsync(pin + 8, d_res, sizeof(SufFold), hipMemcpyDeviceToHost, st));
+    if (bwt) GX_TRY(call, hipMemcpyAsync(bwt, d_bwt.p, N, hipMemcpyDeviceToHost, st));
+    if (sa) GX_TRY(call, hipMemcpyAsync(sa, d_sa, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+    if (lcp) GX_TRY(call, hipMemcpyAsync(lcp, d_lcp, (size_t)N * 4, hipMemcpyDeviceToHost, st));
+    GX_TRY(call, hipStreamSynchronize(st));
+    DevCall::elapsed(ctx->ev0, ctx->ev1, &info.lcp_ms);
+    DevCall::elapsed(ctx->ev1, ctx->ev2, &info.fold_ms);
     SufFold f;
     memcpy(&f, pin + 8, sizeof f);
-    done(GX_OK);   // (the stream is idle)
+    call.done(GX_OK);   // (the stream is idle)
     out->num_internal = f.num_internal;
     out->num_leaves = N;
     out->num_nodes = f.num_internal + N + 1;
@@ -304,9 +308,6 @@ int suffix_device(gx_context* ctx, const uint8_t* t, uint32_t N, gx_suffix_stats
     out->longest_repeat_start = f.repeat_start;
     return GX_OK;
 }
-
-#undef SUF_TRY
-#undef SUF_GET
 
 // Rust's `{}` of an f64: the shortest digits that round-trip, never an exponent.
 std::string suf_f64(double v) {

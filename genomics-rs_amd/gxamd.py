@@ -1095,6 +1095,20 @@ class SuffixIndex:
             packed = np.zeros(1, np.uint8)
         return packed, off, len(off) - 1
 
+    def _grown(self, npat: int, max_hits: int, hoff, call):
+        """The two-try GX_ECAP loop of the three searches: call(cap) allocates its output arrays of cap entries,
+        makes the call with hit_offsets = hoff and returns (rc, arrays).  A first capacity that is too small
+        comes back as GX_ECAP with hoff complete, so its last entry is the capacity of the second try.
+        Returns the arrays of the call that succeeded."""
+        cap = max(1, min(npat * min(max_hits, self.n + 1), _FIRST_CAP))
+        for _ in range(2):
+            rc, out = call(cap)
+            if rc != 7:
+                break
+            cap = int(hoff[-1])   # GX_ECAP: hit_offsets is complete; allocate and repeat
+        _check(rc)
+        return out
+
     def search(self, patterns, max_hits: int = 0) -> dict:
         """gx_suffix_index_search for a batch: `patterns` is a sequence of bytes, or (packed, offsets) with
         pattern p = packed[offsets[p]:offsets[p + 1]].  Returns uint32 arrays "lo", "count", "prefix_len",
@@ -1109,15 +1123,13 @@ class SuffixIndex:
                                                 0, None, 0, None))
         else:
             hoff = np.zeros(npat + 1, np.uint64)
-            cap = max(1, min(npat * min(max_hits, self.n + 1), _FIRST_CAP))
-            for _ in range(2):
+
+            def call(cap):
                 pos = np.zeros(cap, np.uint32)
-                rc = lib().gx_suffix_index_search(self.ptr, packed.ctypes.data, off.ctypes.data, npat, hits.ctypes.data,
-                                                  max_hits, pos.ctypes.data, cap, hoff.ctypes.data)
-                if rc != 7:
-                    break
-                cap = int(hoff[-1])   # GX_ECAP: hit_offsets is complete; allocate and repeat
-            _check(rc)
+                return lib().gx_suffix_index_search(self.ptr, packed.ctypes.data, off.ctypes.data, npat, hits.ctypes.data,
+                                                    max_hits, pos.ctypes.data, cap, hoff.ctypes.data), pos
+
+            pos = self._grown(npat, max_hits, hoff, call)
             out = {"positions": pos[:int(hoff[-1])], "hit_offsets": hoff}
         r = {k: np.ascontiguousarray(hits[k]) for k in ("lo", "count", "prefix_len", "prefix_pos")}
         if out:
@@ -1138,16 +1150,14 @@ class SuffixIndex:
                                                        hits.ctypes.data, 0, None, None, 0, None))
         else:
             hoff = np.zeros(npat + 1, np.uint64)
-            cap = max(1, min(npat * min(max_hits, self.n + 1), _FIRST_CAP))
-            for _ in range(2):
+
+            def call(cap):
                 pos, dst = np.zeros(cap, np.uint32), np.zeros(cap, np.uint8)
-                rc = lib().gx_suffix_index_search_approx(self.ptr, packed.ctypes.data, off.ctypes.data, npat, k,
-                                                         hits.ctypes.data, max_hits, pos.ctypes.data, dst.ctypes.data,
-                                                         cap, hoff.ctypes.data)
-                if rc != 7:
-                    break
-                cap = int(hoff[-1])   # GX_ECAP: hit_offsets is complete; allocate and repeat
-            _check(rc)
+                return lib().gx_suffix_index_search_approx(self.ptr, packed.ctypes.data, off.ctypes.data, npat, k,
+                                                           hits.ctypes.data, max_hits, pos.ctypes.data, dst.ctypes.data,
+                                                           cap, hoff.ctypes.data), (pos, dst)
+
+            pos, dst = self._grown(npat, max_hits, hoff, call)
             out = {"positions": pos[:int(hoff[-1])], "distances": dst[:int(hoff[-1])], "hit_offsets": hoff}
         r = {f: np.ascontiguousarray(hits[f]) for f in ("count", "best_dist", "best_pos", "candidates")}
         if out:
@@ -1169,17 +1179,16 @@ class SuffixIndex:
                                                      hits.ctypes.data, 0, None, None, None, 0, None))
         else:
             hoff = np.zeros(npat + 1, np.uint64)
-            cap = max(1, min(npat * min(max_hits, self.n + 1), _FIRST_CAP))
-            for _ in range(2):
+
+            def call(cap):
                 end, dst = np.zeros(cap, np.uint32), np.zeros(cap, np.uint8)
                 sta = np.zeros(cap, np.uint32) if starts else None
-                rc = lib().gx_suffix_index_search_edit(self.ptr, packed.ctypes.data, off.ctypes.data, npat, k,
-                                                       hits.ctypes.data, max_hits, end.ctypes.data, dst.ctypes.data,
-                                                       sta.ctypes.data if starts else None, cap, hoff.ctypes.data)
-                if rc != 7:
-                    break
-                cap = int(hoff[-1])   # GX_ECAP: hit_offsets is complete; allocate and repeat
-            _check(rc)
+                return lib().gx_suffix_index_search_edit(self.ptr, packed.ctypes.data, off.ctypes.data, npat, k,
+                                                         hits.ctypes.data, max_hits, end.ctypes.data, dst.ctypes.data,
+                                                         sta.ctypes.data if starts else None, cap,
+                                                         hoff.ctypes.data), (end, dst, sta)
+
+            end, dst, sta = self._grown(npat, max_hits, hoff, call)
             tot = int(hoff[-1])
             out = {"ends": end[:tot], "distances": dst[:tot], "starts": sta[:tot] if starts else None,
                    "hit_offsets": hoff}
