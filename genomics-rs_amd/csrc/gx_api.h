@@ -46,7 +46,7 @@ hipError_t launch_fill(int W, int lay, bool local, int planes, bool track, bool 
                        hipStream_t st);
 hipError_t launch_finalize(const PairDev* d_pairs, int npairs, const StripRes* d_sres, PairRes* d_pres,
                            hipStream_t st);
-hipError_t launch_traceback(const TbDev* d_jobs, int njobs, int max_strips, bool w16, bool seq, hipStream_t st);
+hipError_t launch_traceback(const TbDev* d_jobs, int njobs, int max_strips, bool w16, bool seq, bool fast, hipStream_t st);
 hipError_t launch_export(const int32_t* plane, int32_t* out, int n, int m, int t4, int lay, int gshift, int row0,
                          int rows, hipStream_t st);
 hipError_t launch_export_w16(const uint8_t* codes, int half, int which, int32_t* out, int n, int m, int t4, int h,
@@ -176,6 +176,25 @@ struct TbOut {
     const int* sg = nullptr;           // [4 * strips] entry i, entry j, records, active
     const uint32_t* hr = nullptr;      // [strips * kStripRows] records
     double ms = 0;
+    // the sequential walk's launch (gx_walk_info, gx_walk_records)
+    const int* stat = nullptr;         // [2 * jobs] blocks chased, blocks walked by the fixed point
+    size_t strips = 0;                 // strips over all jobs
+    std::vector<int> half;             // job -> its 16-bit half of the twin's code plane
+    int seq = 0, prio = 0, fast = 0;   // tb_seq_kernel ran; its walker priority; the table-driven chase was on
+};
+
+// The sequential walk's run-time properties (tb_seq_kernel, TbDev.prio /
+// TbDev.fast).  overlapped: a fill is queued behind this walk on the rotated
+// pipeline (walk i beside fills i + 1 and i + 2); unpipelined: the caller
+// waits for this walk's records before anything else is enqueued.
+struct WalkPolicy {
+    int prio, fast;
+};
+WalkPolicy walk_policy(bool overlapped, bool unpipelined, size_t njobs);
+struct WalkSeen {   // the last walk collected, for gx_walk_info / gx_walk_records (gx_api_walk.cpp note_walk)
+    int seq = 0, prio = 0, fast = 0, chased = 0, fixed = 0, pairs = 0, cyc_all = 0, cyc_walk = 0;
+    int prios[8] = {-1, -1, -1, -1, -1, -1, -1, -1};   // the last eight sequential walk launches' priorities, the latest last
+    std::vector<uint32_t> words;                       // its records (GX_WALK_RECORDS=1 only)
 };
 
 // Page-locked host buffer, grown on demand (device-to-host copies DMA
@@ -310,6 +329,7 @@ struct gx_context {
     int last_tbl = 0;                                // ... used the small-alphabet score tables (gx_fill_score_table)
     int last_groups = 1;                             // fill launches per pass of the last staged / batch call
     int last_scheme = 0;                             // ... its overlapped pipeline: 0 none, 1 two A buffers and one B, 2 rotation
+    WalkSeen walk_seen;
     // GX_STAGED_PLANE_SUMS: plane checksums of every pass of a staged run
     DevBuf sums_dev;
     unsigned long long* sums_dst = nullptr;          // where the next fill's checksums go (nullptr: off)
@@ -594,7 +614,7 @@ int label_boundary(const HostScores& hs, int is_local, const uint8_t* s1, size_t
 int label_walk_records(const HostScores& hs, int is_local, const uint8_t* s1, size_t n, const uint8_t* s2,
                        size_t m, uint64_t si, uint64_t sj, const TbOut& tb, size_t p, Walk& w);
 int run_traceback(gx_context* ctx, const std::vector<const FillJob*>& jv, const std::vector<TbStart>& starts,
-                  TbOut& out, int slot, bool collect, bool dev_end_E, hipStream_t ts);
+                  TbOut& out, int slot, bool collect, bool dev_end_E, hipStream_t ts, bool overlapped = false);
 int run_traceback(gx_context* ctx, const FillJob& job, const std::vector<TbStart>& starts, TbOut& out,
                   int slot = -1, bool collect = true, bool dev_end_E = false);
 int tb_collect(gx_context* ctx, int slot, size_t P, TbOut& out);

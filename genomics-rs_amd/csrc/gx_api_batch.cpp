@@ -334,8 +334,9 @@ static int batch_core_overlap(gx_context* ctx, const std::vector<PairHost>& ph,
                 HIPCHK(hipEventRecord(ctx->ev1, fs));
             }
             HIPCHK(hipStreamWaitEvent(sT, ctx->slots[rp.fslot].fdone, 0));
+            // (walk i runs beside fills i + 1 and i + 2; the call's last walk beside nothing: walk_policy)
             return run_traceback(ctx, std::vector<const FillJob*>{&j}, gstarts[g], ctx->slots[rp.wslot].out, rp.wslot,
-                                 false, false, sT);
+                                 false, false, sT, i + 1 < N);
         };
         // fill i's results; its buffers back to the pool, though walk i may
         // still read them: their next user's stream waits for that walk

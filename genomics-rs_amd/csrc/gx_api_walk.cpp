@@ -127,6 +127,58 @@ int label_walk_records(const HostScores& hs, int is_local, const uint8_t* s1, si
     return GX_OK;
 }
 
+// The sequential walk's priority and walker (tb_seq_kernel).  A walk with a
+// fill queued behind it on the rotated pipeline shares its CU with a fill
+// band, whose eight waves move in lockstep and feed the bands below them in
+// their twin: what the raised walker takes from one band it takes from the
+// chain, so that walk runs at kWalkPrioOverlapped (DESIGN.md 6.6 has the
+// measurement).  Every other walk -- a call's last walk, which nothing
+// overlaps, and the short-batch pipelines -- keeps priority 3.
+// The table-driven chase is taken where it is measured to win: an
+// unpipelined walk of at most one workgroup a CU, where the walker's latency
+// is the whole cost.  Its instantiation's LDS and registers halve the
+// workgroups a CU of a many-pair launch (1024 x 1k lost 13 %) and stretch a
+// walk beside the fills past the rotation's budget, so those keep the
+// fixed-point kernel.  GX_TB_PRIO=0..3 and GX_TB_FAST=0|1 override.
+static constexpr int kWalkPrioOverlapped = 0;
+static constexpr size_t kWalkFastMaxJobs = 256;   // the CUs of the device
+WalkPolicy walk_policy(bool overlapped, bool unpipelined, size_t njobs) {
+    WalkPolicy w{overlapped ? kWalkPrioOverlapped : 3, unpipelined && !overlapped && njobs <= kWalkFastMaxJobs ? 1 : 0};
+    if (const char* e = getenv("GX_TB_PRIO"); e && e[0] >= '0' && e[0] <= '3' && !e[1]) w.prio = e[0] - '0';
+    if (const char* e = getenv("GX_TB_FAST"); e && (e[0] == '0' || e[0] == '1') && !e[1]) w.fast = e[0] - '0';
+    return w;
+}
+
+// What gx_walk_info / gx_walk_records report of a collected walk: owned
+// copies (nothing keeps a pointer into a slot's pinned block).  The record
+// words are copied only under GX_WALK_RECORDS=1 (verification; 4 B a row).
+static void note_walk(gx_context* ctx, const TbOut& w) {
+    WalkSeen& n = ctx->walk_seen;
+    const size_t P = w.so.size();
+    n.seq = w.seq; n.prio = w.prio; n.fast = w.fast; n.pairs = (int)P;
+    n.chased = n.fixed = n.cyc_all = n.cyc_walk = 0;
+    n.words.clear();
+    if (w.seq)
+        for (size_t p = 0; p < P; ++p) { n.chased += w.stat[2 * p]; n.fixed += w.stat[2 * p + 1]; }
+    if (w.seq && P) { n.cyc_all = (int)((unsigned)w.c[3] >> 16); n.cyc_walk = (int)((unsigned)w.c[3] & 0xFFFFu); }
+    const char* e = getenv("GX_WALK_RECORDS");
+    if (!(e && !strcmp(e, "1"))) return;
+    auto put = [&](uint32_t v) { n.words.push_back(v); };
+    put((uint32_t)P); put((uint32_t)w.srows);
+    for (size_t p = 0; p < P; ++p) {
+        const size_t ns = (p + 1 < P ? w.so[p + 1] : w.strips) - w.so[p];
+        for (int x = 0; x < 3; ++x) put((uint32_t)w.c[4 * p + x]);
+        put(w.seq ? (uint32_t)w.stat[2 * p] : 0u); put(w.seq ? (uint32_t)w.stat[2 * p + 1] : 0u);
+        put((uint32_t)w.half[p]); put((uint32_t)ns);
+        for (size_t s = 0; s < ns; ++s) {
+            const int* g = &w.sg[4 * (w.so[p] + s)];
+            for (int x = 0; x < 4; ++x) put((uint32_t)g[x]);
+            const int nr = g[3] ? std::min(std::max(g[2], 0), w.srows) : 0;
+            for (int q = 0; q < nr; ++q) put(w.hr[(w.so[p] + s) * w.srows + q]);
+        }
+    }
+}
+
 // dev_end_E: take each start cell's landing column from the fill's device
 // results (global mode, start (n, m)), so the traceback can be queued right
 // behind the fill without waiting for its results on the host.
@@ -134,7 +186,7 @@ int label_walk_records(const HostScores& hs, int is_local, const uint8_t* s1, si
 // `starts` over all of them; the fills share layout and code format), its
 // kernels on stream ts (nullptr: the context's stream).
 int run_traceback(gx_context* ctx, const std::vector<const FillJob*>& jv, const std::vector<TbStart>& starts,
-                  TbOut& out, int slot, bool collect, bool dev_end_E, hipStream_t ts) {
+                  TbOut& out, int slot, bool collect, bool dev_end_E, hipStream_t ts, bool overlapped) {
     const size_t P = starts.size();
     const FillJob& job = *jv[0];
     std::vector<const PairDev*> pdv;
@@ -160,15 +212,18 @@ int run_traceback(gx_context* ctx, const std::vector<const FillJob*>& jv, const 
     int rc;
     auto cleanup = [&]() { pool_put(ctx, tbb); pool_put(ctx, jb); };
     const int SR = job_strip_rows(job);
-    const size_t nc = 4 * P, nsg = 4 * std::max<size_t>(stot, 1), nhr = std::max<size_t>(stot, 1) * SR;
-    if ((rc = pool_get(ctx, (nc + nsg) * sizeof(int) + nhr * sizeof(uint32_t), &tbb, ts)) ||
+    // (nst: the sequential walk's block counts, two a pair, zeroed with seg)
+    const size_t nc = 4 * P, nsg = 4 * std::max<size_t>(stot, 1), nst = 2 * P, nhr = std::max<size_t>(stot, 1) * SR;
+    const WalkPolicy wp = walk_policy(overlapped, collect, P);
+    if ((rc = pool_get(ctx, (nc + nsg + nst) * sizeof(int) + nhr * sizeof(uint32_t), &tbb, ts)) ||
         (slot < 0 && (rc = pool_get(ctx, P * sizeof(TbDev), &jb, ts)))) {
         cleanup();
         return rc;
     }
     int* const cnt_d = (int*)tbb.p;
     int* const seg_d = cnt_d + nc;
-    uint32_t* const recs_d = (uint32_t*)(seg_d + nsg);
+    int* const stat_d = seg_d + nsg;
+    uint32_t* const recs_d = (uint32_t*)(stat_d + nst);
     for (size_t p = 0; p < P; ++p) {
         TbDev& t = jobs[p];
         const PairDev& d = *pdv[p];
@@ -188,6 +243,9 @@ int run_traceback(gx_context* ctx, const std::vector<const FillJob*>& jv, const 
         t.w16 = job.nocodes ? (const uint8_t*)d.pI : nullptr;   // the twin's code plane (shared by its pairs)
         t.w16_half = d.twin_half;
         t.t4 = d.t4;
+        t.prio = wp.prio;
+        t.fast = wp.fast;
+        t.stat = stat_d + 2 * p;
     }
     (void)presv;
     const size_t jbytes = P * sizeof(TbDev);
@@ -215,18 +273,18 @@ int run_traceback(gx_context* ctx, const std::vector<const FillJob*>& jv, const 
             else ctx->slots[slot].tjob_last.clear();
         }
     }
-    if (e == hipSuccess) e = hipMemsetAsync(seg_d, 0, nsg * sizeof(int), ts);
+    if (e == hipSuccess) e = hipMemsetAsync(seg_d, 0, (nsg + nst) * sizeof(int), ts);
     hipEvent_t evb = slot >= 0 ? ctx->slots[slot].tb : ctx->ev1, eve = slot >= 0 ? ctx->slots[slot].te : ctx->ev2;
     if (e == hipSuccess) e = hipEventRecord(evb, ts);
-    if (e == hipSuccess) e = launch_traceback((const TbDev*)jdev, (int)P, max_strips, job.nocodes, job.noskel, ts);
+    if (e == hipSuccess) e = launch_traceback((const TbDev*)jdev, (int)P, max_strips, job.nocodes, job.noskel, wp.fast != 0, ts);
     if (e == hipSuccess) e = hipEventRecord(eve, ts);
-    // one pinned host block: c | sg | hr
-    const size_t bytes = (nc + nsg) * sizeof(int) + nhr * sizeof(uint32_t);
+    // one pinned host block: c | sg | stat | hr
+    const size_t bytes = (nc + nsg + nst) * sizeof(int) + nhr * sizeof(uint32_t);
     PinnedBuf& recpin = slot >= 0 ? ctx->slots[slot].tbpin : ctx->tb_pin;
     if (e == hipSuccess && !pinned_grow(recpin, bytes)) e = hipErrorOutOfMemory;
     int* c = (int*)recpin.p;
     int* sg = c + nc;
-    uint32_t* hr = (uint32_t*)(sg + nsg);
+    uint32_t* hr = (uint32_t*)(sg + nsg + nst);
     using clk = std::chrono::steady_clock;
     const auto q0 = clk::now();
     // pipelined: the record copies go on the copy stream after the traceback
@@ -239,6 +297,16 @@ int run_traceback(gx_context* ctx, const std::vector<const FillJob*>& jv, const 
     out.c = c; out.sg = sg; out.hr = hr;
     out.so = so;
     out.srows = SR;
+    out.stat = sg + nsg;
+    out.strips = stot;
+    out.half.resize(P);
+    for (size_t p = 0; p < P; ++p) out.half[p] = jobs[p].w16_half;
+    out.seq = job.noskel ? 1 : 0; out.prio = wp.prio; out.fast = wp.fast;
+    if (out.seq) {   // the last eight sequential walks' priorities, as launched
+        int* pr = ctx->walk_seen.prios;
+        std::copy(pr + 1, pr + 8, pr);
+        pr[7] = wp.prio;
+    }
     if (!collect) {   // pipelined: tb_collect() waits for the records later
         if (e == hipSuccess) e = hipEventRecord(ctx->slots[slot].tdone, cs);
         DevBuf* h = ctx->slots[slot].held;
@@ -266,6 +334,7 @@ int run_traceback(gx_context* ctx, const std::vector<const FillJob*>& jv, const 
         out.end_j[p] = c[4 * p + 1];
         if (out.end_i[p] < 0) return fail(GX_EHIP, "traceback: landing column out of range (incomplete fill)");
     }
+    note_walk(ctx, out);
     return GX_OK;
 }
 
@@ -288,9 +357,29 @@ int tb_collect(gx_context* ctx, int slot, size_t P, TbOut& out) {
         out.end_j[p] = out.c[4 * p + 1];
         if (out.end_i[p] < 0) return fail(GX_EHIP, "traceback: landing column out of range (incomplete fill)");
     }
+    note_walk(ctx, out);
     if (const char* lg = getenv("GX_LOG"); lg && !strcmp(lg, "debug") && P)
         fprintf(stderr, "[gx DEBUG] traceback %.3f ms; pair 0 diag word %u (%u cycles per block, %u walking)\n", ms,
                 (unsigned)out.c[3], (unsigned)out.c[3] >> 16, (unsigned)out.c[3] & 0xFFFFu);
+    return GX_OK;
+}
+
+extern "C" int gx_walk_info(const gx_context* ctx, int* out16) {
+    if (!ctx || !out16) return fail(GX_EINVAL, "gx_walk_info: NULL argument");
+    const WalkSeen& n = ctx->walk_seen;
+    const int v[8] = {n.seq, n.prio, n.fast, n.chased, n.fixed, n.pairs, n.cyc_all, n.cyc_walk};
+    std::copy(v, v + 8, out16);
+    if (!n.seq) std::fill(out16 + 1, out16 + 8, 0);
+    std::copy(n.prios, n.prios + 8, out16 + 8);
+    return GX_OK;
+}
+
+extern "C" int gx_walk_records(const gx_context* ctx, uint32_t* out, size_t cap, size_t* n_words) {
+    if (!ctx || !n_words) return fail(GX_EINVAL, "gx_walk_records: NULL argument");
+    const std::vector<uint32_t>& w = ctx->walk_seen.words;
+    if (w.empty()) return fail(GX_EINVAL, "gx_walk_records: no walk was collected under GX_WALK_RECORDS=1 on this context");
+    if (out) std::copy(w.begin(), w.begin() + std::min(cap, w.size()), out);
+    *n_words = w.size();
     return GX_OK;
 }
 

@@ -198,6 +198,12 @@ struct TbDev {           // per-pair traceback job
     int t4;                // 4-step groups per strip
     const int* start_ij_dev;// local twin fill in the overlapped pipeline: the start cell {i, j} read on the device
                            // (PairRes.lmax_i / lmax_j after finalize_kernel: no host round trip); tb_seq_kernel only
+    // tb_seq_kernel only (gx_api_walk.cpp walk_policy): the walker wave's
+    // s_setprio level, 0..3; fast != 0: the table-driven block chase where a
+    // block allows it, the fixed-point walk elsewhere; stat (or nullptr):
+    // out, {blocks chased, blocks walked by the fixed point}
+    int prio, fast;
+    int* stat;
 };
 
 // ---- wide (int64) fill (gx_wide.hip): jobs outside the exact-int32 range --

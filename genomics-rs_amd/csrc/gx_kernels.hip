@@ -1377,6 +1377,24 @@ __global__ __launch_bounds__(64) void tb_strip_kernel(const TbDev* __restrict__ 
 // per-row "nearest non-insert" table in LDS, ~475 with the window transposed
 // into registers (row r's words in the lanes of Wr[r], two v_readlane a row)
 // -- a lone wave's instruction latency, not the memory, sets a row's cost.
+// All of them derived a row's move from the window words at walk time.  The
+// table-driven chase (TbDev.fast, tb_seq_window_tab / tb_chase_block below)
+// leaves that to the helpers: they write a byte per row and window step that
+// holds the row's whole column shift, and the walker's dependent chain per
+// row is one LDS byte, a shift and a subtraction (8.5 instructions a row in
+// all, ~130 cycles).  Blocks it cannot take -- the walk's first, an escape
+// byte, an entry below the window, a path that reaches column 0 -- go to the
+// fixed point above, which is thus the fallback and the reference: the
+// records are equal word for word (tests/test_gpu_walk_chase.py).  Measured
+// on 16 unpipelined 30k pairs (tools/walk_cycles.py): the walker's cycles a
+// block 22.4-23.1k -> 11.1-11.5k with one block in ten given back, but the
+// block period only 23.3-24.0k -> 17.3-17.6k: the helpers' window and table
+// (48 steps a lane) now set the pace.  The chase costs LDS and registers
+// (9.2 -> 34.6 KB, 59 -> 95 VGPRs), so it is an instantiation of its own and
+// the host takes it only for an unpipelined walk of at most one workgroup a
+// CU (gx_api_walk.cpp walk_policy): beside the fills that footprint
+// stretched the walks from 5.8-6.1 to 7-14 ms, past the rotation's budget,
+// and on 1024 x 1k it halved the workgroups a CU (13 % slower).
 // Layout 0 only.
 constexpr int kSqWin = 12;
 constexpr int kSqHelp = 4;
@@ -1403,9 +1421,121 @@ __device__ __forceinline__ void tb_seq_window(const TbDev& J, const int vb, cons
 #pragma unroll
     for (int u = 0; u < kPer; ++u) lw[(hw + u * kSqHelp) * kWave + lane] = w16_word_of(w4[u], sh);
 }
+// The table-driven walk (TbDev.fast).  A row entered at column g leaves it at
+// g - d, d = 1 + run - del: run = the insert run at the entry step, del = the
+// move after the run is a delete.  For block k + 1 the helpers write, beside
+// the window words, one byte per row and step of the window, (d << 1) | del
+// (run <= 126: d <= 127, and d = 127 comes with del = 0), or kSqEsc where the
+// chase must not go on: run >= 127, no non-insert step at or below the step
+// inside the window (the run leaves its low edge), or that step lies before
+// the row's column 1 (the run reaches column 0).  (d, not the run, so that
+// the walker's dependent chain per row is a shift and a subtraction.)  A
+// row's 192 bytes are followed by four kSqEsc bytes: an entry outside the
+// window reads the first of them (tb_chase_block).  Here a helper takes 16
+// rows, and its lanes' quarters (lane >> 4) three words each of a row, so the
+// "nearest non-insert step below" of a row crosses the quarters inside one
+// wave (three lane reads) and needs no barrier between the helpers.  Every
+// byte of the table is written for every block.
+constexpr int kSqSteps = 16 * kSqWin;    // steps a row of the table
+constexpr int kSqRowB = kSqSteps + 4;    // bytes a row: its steps and the escape pad
+constexpr int kSqEsc = 0xFF;
+static_assert(kSqHelp == 4 && kSqWin % 4 == 0 && kSqHelp * 16 == kTbRows, "helper row / quarter split");
+static_assert(kSqRowB % 4 == 0 && (kSqSteps / 4) % 4 == 0, "a row and a quarter's bytes are whole dwords");
+__device__ __forceinline__ void tb_seq_window_tab(const TbDev& J, const int vb, const int q0, uint32_t* buf, uint8_t* tab,
+                                                  const int hw, const int lane) {
+    typedef __attribute__((address_space(3))) uint32_t lu32w;
+    lu32w* const lw = (lu32w*)(uintptr_t)lds_addr(buf);
+    lu32w* const lt = (lu32w*)(uintptr_t)lds_addr(tab);
+    const int row = 16 * hw + (lane & 15), qt = lane >> 4;
+    const int s = tb_strip_of(J, vb), rho = tb_rho(J, vb, row), sh = 16 * J.w16_half;
+    const int lo_rel = tb_lot(J, rho) - 16 * q0;   // the step of column 1, from the window's first step
+    constexpr int kPer = kSqWin / 4;
+    uint4 w4[kPer][4];
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) {
+        const int q = min(q0 + qt * kPer + u, J.t16 - 1);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) w4[u][g] = w16_group(J, s, 4 * q + g, rho);
+    }
+    uint32_t w[kPer];
+    int own = -1;   // the highest non-insert step of this lane's words, (step in window << 1) | del
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) {
+        w[u] = w16_word_of(w4[u], sh);
+        lw[(qt * kPer + u) * kWave + row] = w[u];
+        const uint32_t m = ((w[u] >> 16) | ~w[u]) & 0xFFFFu;
+        const int k = 15 - (int)__builtin_ctz(m | 0x10000u);
+        const int cand = ((16 * (qt * kPer + u) + k) << 1) | (int)((w[u] >> ((31 - k) & 31)) & 1u);
+        own = m ? cand : own;
+    }
+    // the nearest one below this lane's words: the row's lower quarters, the nearest first
+    int last = -1;
+#pragma unroll
+    for (int d = 3; d >= 1; --d) {
+        const int o = __shfl(own, (lane - 16 * d) & (kWave - 1), kWave);
+        last = (qt >= d && o >= 0) ? o : last;
+    }
+    if (qt == 3) lt[(row * kSqRowB + kSqSteps) >> 2] = 0xFFFFFFFFu;   // the row's escape pad
+#pragma unroll
+    for (int u = 0; u < kPer; ++u) {
+#pragma unroll 1   // (unrolled, the 48 steps' independent halves are all computed ahead: ~130 more VGPRs)
+        for (int c = 0; c < 4; ++c) {
+            uint32_t pk = 0;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int i = 4 * c + b;                     // step in word: bit 15 - i
+                const int k = 16 * (qt * kPer + u) + i;      // step in window
+                const bool non_i = (((w[u] >> 16) | ~w[u]) >> (15 - i)) & 1u;
+                const int here = (k << 1) | (int)((w[u] >> (31 - i)) & 1u);
+                last = non_i ? here : last;
+                const int run = k - (last >> 1), del = last & 1;
+                const bool esc = last < 0 || run >= 127 || (last >> 1) < lo_rel;
+                const uint32_t e = esc ? (uint32_t)kSqEsc : (uint32_t)(((1 + run - del) << 1) | del);
+                pk |= e << (8 * b);
+            }
+            lt[(row * kSqRowB + 16 * (qt * kPer + u) + 4 * c) >> 2] = pk;
+        }
+    }
+}
+// The chase of one whole block (entered at lane 63, column ce) through the
+// byte table CB: one dependent LDS byte a row on wave-uniform values.  rel:
+// per lane, its row's table index of column 0 (lo_t - 1 - 16 q0), so row r's
+// byte of column g is at g + rel(r) of its 192.  Going up a block neither g
+// nor rel grows, so the index only falls: it starts inside the window, and
+// below it (as an unsigned number, far above) it reads the row's escape pad.
+// gcol: LDS, [64], each row's entry column for its lane.  False: the block
+// is not the chase's (an escape byte or an entry below the window on any
+// row, a column < 1 at its end and so perhaps before); nothing but gcol was
+// written.  True: g_out = the column after lane 0's move.
+template <int CB>
+__device__ __forceinline__ bool tb_chase_block(uint8_t (*btab)[kTbRows * kSqRowB], int* gcol, const int rel, const int ce,
+                                               int& g_out) {
+    typedef __attribute__((address_space(3))) uint8_t lu8;
+    const lu8* const lt = (const lu8*)(uintptr_t)lds_addr(btab[CB]);
+    lint* const gl = (lint*)(uintptr_t)lds_addr(gcol);
+    int g = ce;
+    unsigned seen = 0;   // the largest byte met
+#pragma unroll
+    for (int r = kTbRows - 1; r >= 0; --r) {
+        gl[r] = g;       // (every lane the same word)
+        const unsigned off = (unsigned)(g + __builtin_amdgcn_readlane(rel, r));
+        const unsigned e = lt[r * kSqRowB + min(off, (unsigned)kSqSteps)];
+        seen = max(seen, e);
+        g -= (int)(e >> 1);
+    }
+    g_out = g;
+    return __builtin_amdgcn_readfirstlane((int)(seen != (unsigned)kSqEsc && g >= 1)) != 0;
+}
+// FAST: the instantiation with the chase (its byte tables, 34.6 KB of LDS and
+// 95 VGPRs in all); the other is the fixed-point walk alone at 9.2 KB and 59
+// VGPRs, which is what a walk beside the fills and a launch of many
+// workgroups a CU need (launch_traceback takes TbDev.fast of the launch).
+template <bool FAST>
 __global__ __launch_bounds__((1 + kSqHelp) * kWave) void tb_seq_kernel(const TbDev* __restrict__ jobs) {
     __shared__ uint32_t wbuf[2][kSqWin * kWave];
     __shared__ int tbl[kSqWin * kWave];
+    __shared__ __attribute__((aligned(16))) uint8_t btab[2][FAST ? kTbRows * kSqRowB : 4];   // the chase's byte tables, 12.25 KB each
+    __shared__ int gcol[FAST ? kTbRows : 1];
     __shared__ SqCtl ctl;
     const TbDev J = jobs[blockIdx.x];
     const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / kWave);
@@ -1421,10 +1551,16 @@ __global__ __launch_bounds__((1 + kSqHelp) * kWave) void tb_seq_kernel(const TbD
     // the walker wave issues ahead of its helpers and of a fill sharing the
     // CU (the walk runs beside the next pass's fill): 1024 x 1k 0.84 -> 0.83
     // ms a pass with the walk on its own stream, 0.94 -> 0.90 without
-    // (tools/walk_prio_ab.sh)
-#ifndef GX_TB_NOPRIO
-    if (wave == 0) __builtin_amdgcn_s_setprio(3);
-#endif
+    // (tools/walk_prio_ab.sh).  The level is the launch's (TbDev.prio, the
+    // host's policy: gx_api_walk.cpp walk_policy); s_setprio takes a constant.
+    if (wave == 0) {
+        switch (J.prio) {
+            case 1: __builtin_amdgcn_s_setprio(1); break;
+            case 2: __builtin_amdgcn_s_setprio(2); break;
+            case 3: __builtin_amdgcn_s_setprio(3); break;
+            default: break;
+        }
+    }
     // block 0 of the walk: its window from every wave
     int vb = (i - 1) / kTbRows, R = (i - 1) % kTbRows, ce = j;
     int q0 = max(((ce - 1 + tb_lot(J, tb_rho(J, vb, R))) >> 4) - (kSqWin - 1), 0);
@@ -1434,22 +1570,48 @@ __global__ __launch_bounds__((1 + kSqHelp) * kWave) void tb_seq_kernel(const TbD
     int s = first, nrec = 0, cb = 0;
     int end_i = -1, end_j = -1;
     long long clk0 = stamp_clk(), walk_clk = 0;   // (diagnostics: end_ij[3])
-    int nblk = 0;
+    int nblk = 0, nchase = 0;
     __syncthreads();
     for (int guard = 0; guard <= (J.strips << tb_bsh(J)) + 2; ++guard) {
         // the next block in the walk is always vb - 1 (the strip above once vb
         // is its strip's top block); its window ends at this block's entry
         const int qn = vb > 0 ? max(((ce - 1 + tb_lot(J, tb_rho(J, vb - 1, kTbRows - 1))) >> 4) - (kSqWin - 1), 0) : 0;
         if (wave > 0) {
-            if (vb > 0) tb_seq_window(J, vb - 1, qn, wbuf[cb ^ 1], wave - 1, lane);
+            if (vb > 0) {
+                if constexpr (FAST) tb_seq_window_tab(J, vb - 1, qn, wbuf[cb ^ 1], btab[cb ^ 1], wave - 1, lane);
+                else tb_seq_window(J, vb - 1, qn, wbuf[cb ^ 1], wave - 1, lane);
+            }
         } else {
             const int vb_top = s << tb_bsh(J);
             guint* const recs = (guint*)(J.recs + (size_t)s * J.srows);
             int nj;
             bool run_end;
             const long long w0 = stamp_clk();
-            const int E = tb_walk_block<kSqWin, true>(J, s, vb, vb_top, R, ce, q0, (const lu32*)(uintptr_t)lds_addr(wbuf[cb]),
-                                                      ltbl, lane, recs, nrec, nj, run_end);
+            // the chase takes whole blocks after the walk's first (entered at
+            // lane 63, their table written by the helpers); a strip's top
+            // block too: its lane 0's move leaves the strip exactly as the
+            // fixed point's top_row does (E = 0, the same 64 records)
+            bool chased = false;
+            int E = -1;
+            if constexpr (FAST) if (guard > 0) {
+                typedef __attribute__((address_space(3))) uint8_t lu8;
+                const int rel = tb_lot(J, tb_rho(J, vb, lane)) - 1 - 16 * q0;
+                int g_out;
+                chased = cb ? tb_chase_block<1>(btab, gcol, rel, ce, g_out) : tb_chase_block<0>(btab, gcol, rel, ce, g_out);
+                if (chased) {   // every lane's record from its own byte (tb_walk_block's rec of a row that goes on)
+                    const int g_in = ((lint*)(uintptr_t)lds_addr(gcol))[lane];
+                    const int e = ((const lu8*)(uintptr_t)lds_addr(btab[cb]))[lane * kSqRowB + g_in + rel];
+                    const int del = e & 1, run = (e >> 1) - 1 + del;
+                    recs[nrec + (kTbRows - 1 - lane)] = (uint32_t)((run << 2) | (del << 1));
+                    nrec += kTbRows;
+                    nj = g_out; run_end = false;
+                    E = vb == vb_top ? 0 : -1;
+                    ++nchase;
+                }
+            }
+            if (!chased)
+                E = tb_walk_block<kSqWin, true>(J, s, vb, vb_top, R, ce, q0, (const lu32*)(uintptr_t)lds_addr(wbuf[cb]),
+                                                ltbl, lane, recs, nrec, nj, run_end);
             walk_clk += stamp_clk() - w0;
             ++nblk;
             int done = 0;
@@ -1481,6 +1643,7 @@ __global__ __launch_bounds__((1 + kSqHelp) * kWave) void tb_seq_kernel(const TbD
         // cycles per block: all (high 16 bits) and the walk's (low 16)
         const long long all = (stamp_clk() - clk0) / max(nblk, 1), wk = walk_clk / max(nblk, 1);
         J.end_ij[3] = (int)((min(all, 65535LL) << 16) | min(wk, 65535LL));
+        if (J.stat) { J.stat[0] = nchase; J.stat[1] = nblk - nchase; }
     }
 }
 
@@ -1751,9 +1914,10 @@ hipError_t launch_finalize(const PairDev* d_pairs, int npairs, const StripRes* d
     return hipGetLastError();
 }
 
-hipError_t launch_traceback(const TbDev* d_jobs, int njobs, int max_strips, bool w16, bool seq, hipStream_t st) {
+hipError_t launch_traceback(const TbDev* d_jobs, int njobs, int max_strips, bool w16, bool seq, bool fast, hipStream_t st) {
     if (seq) {   // no skeleton: the strips walked in sequence (twin plane codes only)
-        hipLaunchKernelGGL(tb_seq_kernel, dim3(njobs), dim3((1 + kSqHelp) * kWave), 0, st, d_jobs);
+        if (fast) hipLaunchKernelGGL(tb_seq_kernel<true>, dim3(njobs), dim3((1 + kSqHelp) * kWave), 0, st, d_jobs);
+        else hipLaunchKernelGGL(tb_seq_kernel<false>, dim3(njobs), dim3((1 + kSqHelp) * kWave), 0, st, d_jobs);
         return hipGetLastError();
     }
     hipLaunchKernelGGL(tb_chase_kernel, dim3(njobs), dim3(64), 0, st, d_jobs);

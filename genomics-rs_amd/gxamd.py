@@ -87,7 +87,7 @@ EXPORTED = ["gx_last_error", "gx_version", "gx_context_create", "gx_context_dest
             "gx_table_plane_sums", "gx_retrace", "gx_table_free", "gx_align", "gx_align_batch", "gx_align_batch_multi",
             "gx_stage_pairs",
             "gx_run_staged", "gx_run_staged_steps", "gx_staged_plane_sums", "gx_staged_steps",
-            "gx_staged_pass_results", "gx_fill_info", "gx_batch_chunks", "gx_fill_twin", "gx_fill_groups", "gx_overlap_scheme", "gx_overlap_rotate_plan", "gx_fill_plane_bits", "gx_plane_bytes_per_cell", "gx_twin_admission",
+            "gx_staged_pass_results", "gx_fill_info", "gx_walk_info", "gx_walk_records", "gx_batch_chunks", "gx_fill_twin", "gx_fill_groups", "gx_overlap_scheme", "gx_overlap_rotate_plan", "gx_fill_plane_bits", "gx_plane_bytes_per_cell", "gx_twin_admission",
             "gx_twin_admission_mode", "gx_twin_admission_rows", "gx_fill_rows", "gx_fill_score_table", "gx_plan_layout",
             "gx_plan_twin_rows", "gx_staged_table",
             "gx_fasta_load",
@@ -144,6 +144,8 @@ def lib():
     L.gx_run_staged_steps.argtypes = [vp, ctypes.POINTER(CScores), ctypes.c_int, ctypes.c_int, ctypes.c_uint32,
                                       ctypes.c_int, vp, ctypes.POINTER(ctypes.c_double)]
     L.gx_fill_info.argtypes = [vp] + [ctypes.POINTER(ctypes.c_int)] * 3
+    L.gx_walk_info.argtypes = [vp, ctypes.POINTER(ctypes.c_int)]
+    L.gx_walk_records.argtypes = [vp, vp, sz, ctypes.POINTER(sz)]
     L.gx_batch_chunks.argtypes = [vp]
     L.gx_fill_twin.argtypes = [vp]
     L.gx_fill_groups.argtypes = [vp]
@@ -437,6 +439,41 @@ class Context:
                 "groups": lib().gx_fill_groups(self.ptr),
                 "twin_rows": lib().gx_fill_rows(self.ptr) if hasattr(lib(), "gx_fill_rows") else 2,
                 "score_table": lib().gx_fill_score_table(self.ptr) if hasattr(lib(), "gx_fill_score_table") else -1}
+
+    def walk_info(self) -> dict:
+        """The last device walk collected (gx_walk_info): whether it was the sequential strip walk,
+        its walker priority, the table-driven chase's switch and block counts, pair 0's cycles a block,
+        and the priorities of the last sequential walks launched (up to eight, the latest last)."""
+        v = (ctypes.c_int * 16)()
+        _check(lib().gx_walk_info(self.ptr, v))
+        d = dict(zip(("sequential", "prio", "fast", "blocks_chased", "blocks_fixed_point", "pairs",
+                      "cycles_per_block", "walk_cycles_per_block"), (int(x) for x in v[:8])))
+        d["launch_prios"] = [int(x) for x in v[8:] if x >= 0]
+        return d
+
+    def walk_records(self) -> list:
+        """That walk's records (kept under GX_WALK_RECORDS=1), per pair (gx_walk_records): {"end": (i, j), "first_strip", "blocks_chased",
+        "blocks_fixed_point", "half", "strips": [((entry i, entry j, records, active), [record words])]}."""
+        n = ctypes.c_size_t()
+        _check(lib().gx_walk_records(self.ptr, None, 0, ctypes.byref(n)))
+        buf = np.zeros(n.value, np.uint32)
+        _check(lib().gx_walk_records(self.ptr, buf.ctypes.data, buf.size, ctypes.byref(n)))
+        w = buf.view(np.int32).tolist()
+        out, k = [], 2
+        for _ in range(w[0]):
+            ei, ej, first, chased, fixed, half, ns = w[k:k + 7]
+            k += 7
+            strips = []
+            for _s in range(ns):
+                seg = tuple(w[k:k + 4])
+                k += 4
+                nr = min(max(seg[2], 0), w[1]) if seg[3] else 0
+                strips.append((seg, w[k:k + nr]))
+                k += nr
+            out.append({"end": (ei, ej), "first_strip": first, "blocks_chased": chased, "blocks_fixed_point": fixed,
+                        "half": half, "strips": strips})
+        assert k == len(w)
+        return out
 
     def overlap_scheme(self) -> int:
         """Which overlapped pipeline the last staged / batch call ran (gx_overlap_scheme):

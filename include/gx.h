@@ -250,6 +250,26 @@ int gx_fill_info(const gx_context* ctx, int* layout, int* band_waves, int* plane
  * plane codes, 24: compact bytes, 96: int32 planes, 192: int64 planes), or
  * -1 without a context.  No reference counterpart (measurement only). */
 int gx_fill_plane_bits(const gx_context* ctx);
+/* The last device walk collected on ctx, out16 = {1 when it was the
+ * sequential strip walk of a twin fill without landing columns (else 0 and
+ * zeros up to [7]), the walker wave's priority 0..3, 1 when it ran the
+ * kernel with the table-driven block chase, blocks the chase took over all
+ * pairs, blocks the fixed-point walk took (every pair's first block, and
+ * every block the chase gave back), pairs, pair 0's cycles per block in all,
+ * and walking; [8..15]: the priorities of the last eight sequential walks
+ * launched on ctx, the latest last (-1: none)}.  The policy: priority 0 for
+ * a walk with a fill queued behind it on the rotated pipeline and 3
+ * elsewhere, the chase for an unpipelined walk of at most 256 pairs;
+ * GX_TB_PRIO=0..3 and GX_TB_FAST=0|1 override.  Measurement only. */
+int gx_walk_info(const gx_context* ctx, int* out16);
+/* The records of that walk as 32-bit words, for comparing two walkers word
+ * for word: {pairs, rows per strip}, then per pair {end i, end j, first
+ * strip, blocks chased, blocks walked by the fixed point, its 16-bit half of
+ * the twin's code plane, strips} and per strip {entry i, entry j, records,
+ * active} followed by that strip's records.  Kept only for walks collected
+ * under GX_WALK_RECORDS=1 (GX_EINVAL otherwise).  Writes at most cap words
+ * and sets *n_words to the count needed.  Verification only. */
+int gx_walk_records(const gx_context* ctx, uint32_t* out, size_t cap, size_t* n_words);
 /* Chunks of the last gx_run_staged(_steps) / gx_align_batch call: a batch
  * whose device footprint (planes, codes, skeleton) exceeds the free HBM runs
  * as contiguous chunks of pairs through the same device buffers

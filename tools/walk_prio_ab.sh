@@ -1,7 +1,7 @@
 #!/bin/bash
-# GPU box: the walker wave's priority (default build vs gpurun_exp/noprio,
-# built with -DGX_TB_NOPRIO) and the walk's own stream (GX_TB_OWN_STREAM=0:
-# on the fill's stream), one bench line each.
+# GPU box: the walker wave's priority (the policy's vs GX_TB_PRIO=0, a
+# run-time property of the walk's launch: TbDev.prio) and the walk's own
+# stream (GX_TB_OWN_STREAM=0: on the fill's stream), one bench line each.
 set -o pipefail
 cd "$GRAFT_REPO_ROOT"; mkdir -p gpurun_out/wp
 one() {   # name env... -- bench args
@@ -12,14 +12,13 @@ one() {   # name env... -- bench args
       || { echo "FAIL $name"; tail -5 gpurun_out/wp/$name.err; exit 1; }
   python3 -c "import json;d=json.load(open('gpurun_out/wp/$name.json'));p=d.get('parity',{});lb=d.get('local_batch',{});print('$name', d['value'], d['ms_per_step'], d['roofline'].get('fill_ms_avg'), p.get('pairs_checked'), p.get('bit_exact'), 'local', lb.get('gcups'), flush=True)"
 }
-NP=$GRAFT_REPO_ROOT/gpurun_exp/noprio/libgx_amd.so
 for L in 1024 4096; do
   A="--length $L --pairs-per-gpu 1024 --steps 20 --local-batch-steps 0"
   one def$L X=1 -- $A
-  one noprio$L GX_LIB=$NP -- $A
+  one noprio$L GX_TB_PRIO=0 -- $A
   one samestream$L GX_TB_OWN_STREAM=0 -- $A
 done
 one def_head X=1 -- --steps 10
-one noprio_head GX_LIB=$NP -- --steps 10
+one noprio_head GX_TB_PRIO=0 -- --steps 10
 one def_avsa X=1 -- --workload allvsall --planes --steps 10 --local-batch-steps 0
-one noprio_avsa GX_LIB=$NP -- --workload allvsall --planes --steps 10 --local-batch-steps 0
+one noprio_avsa GX_TB_PRIO=0 -- --workload allvsall --planes --steps 10 --local-batch-steps 0
