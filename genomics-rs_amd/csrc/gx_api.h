@@ -369,6 +369,9 @@ struct gx_context {
     // the last matching-statistics or MEM call (gx_match_info; gx_api_match.cpp)
     uint64_t mat_cands = 0, mat_kept = 0, mat_words = 0;
     double mat_stats_ms = 0.0, mat_seed_ms = 0.0, mat_emit_ms = 0.0;
+    // the last extend call (gx_extend_info; gx_api_extend.cpp)
+    uint64_t ext_hits = 0, ext_cells = 0, ext_trace_bytes = 0, ext_chunks = 0;
+    double ext_fill_ms = 0.0, ext_walk_ms = 0.0;
 };
 
 // search mode's index (gx_api_search.cpp builds and frees it; gx_api_match.cpp reads it)

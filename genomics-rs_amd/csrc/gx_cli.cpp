@@ -38,7 +38,7 @@
 //       checked as the reference's tree checks it; --suffix-links is accepted
 //       and ignored; the Graphviz block of small trees is not printed.
 //
-//   gx-align search -f genome.fasta -p patterns.fasta [--max-hits K] [-k MISMATCHES | -e EDITS] [-o hits.tsv]
+//   gx-align [-c config.toml] search -f genome.fasta -p patterns.fasta [--max-hits K] [-k MISMATCHES | -e EDITS [--cigar]] [-o hits.tsv]
 //       No counterpart in the reference's main.rs: where every record of
 //       patterns.fasta occurs in the first record of genome.fasta, from a
 //       suffix index kept on the GPU (gx_suffix_index_search).
@@ -52,6 +52,10 @@
 //       most that many substitutions, insertions and deletions
 //       (gx_suffix_index_search_edit); the line is then name,
 //       length, count, best_dist, best_end and up to K start-end:dist triples.
+//       With --cigar (with -e alone) every reported window is aligned to its
+//       pattern on the band of EDITS diagonals under the scores of the config
+//       file (gx_suffix_index_extend) and a triple becomes
+//       start-end:dist:score:CIGAR.
 //   gx-align search -f genome.fasta -p queries.fasta --mem L [-o mems.tsv]
 //       (not together with -k or -e) Every maximal exact match of L bases or
 //       more between a record of queries.fasta, of any length, and the genome
@@ -83,7 +87,7 @@ void usage() {
             "       gx-align compare -d|--fasta-dir <DIR> [-o <TSV>]\n"
             "       gx-align suffix-tree -f|--fasta-path <FASTA> [-a|--alphabet-file <ALPHABET>] [--suffix-links] "
             "[--stats] [-o <BWT>]\n"
-            "       gx-align search -f|--fasta-path <GENOME> -p|--patterns <PATTERNS> [--max-hits <K>] [-k <MISMATCHES> | -e <EDITS>] [-o <TSV>]\n"
+            "       gx-align search -f|--fasta-path <GENOME> -p|--patterns <PATTERNS> [--max-hits <K>] [-k <MISMATCHES> | -e <EDITS> [--cigar]] [-o <TSV>]\n"
             "       gx-align search -f|--fasta-path <GENOME> -p|--patterns <QUERIES> --mem <MIN_LEN> [-o <TSV>]\n");
 }
 
@@ -464,9 +468,10 @@ int run_suffix_tree(const std::string& fasta, const std::string& alphabet, bool 
 // Search mode on GPU 0 (no counterpart in the reference): every record of the
 // pattern file against the suffix index of the genome's first record.
 // -k K: at most K substitutions (gx_suffix_index_search_approx); -e K: at most K
-// differences (gx_suffix_index_search_edit); both below 0: exact.
+// differences (gx_suffix_index_search_edit); both below 0: exact.  sc (with -e alone): the
+// reported windows are aligned under these scores on the band of K (gx_suffix_index_extend).
 int run_search(const std::string& fasta, const std::string& patterns, uint32_t max_hits, const std::string& out_path,
-               int kmis, int kedit) {
+               int kmis, int kedit, const gx_scores* sc) {
     const char* lg = getenv("GX_LOG");
     const bool info = lg && (!strcmp(lg, "info") || !strcmp(lg, "debug"));
     if (info) fprintf(stderr, "[INFO] MODE: Search\n[INFO] Loading sequences from %s and %s\n", fasta.c_str(), patterns.c_str());
@@ -515,6 +520,31 @@ int run_search(const std::string& fasta, const std::string& patterns, uint32_t m
         if (kedit >= 0) sta.assign((size_t)hoff[npat], 0);
     }
     const auto us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+    std::vector<gx_extend_hit> xhits;
+    std::vector<uint64_t> coff;
+    std::vector<uint32_t> cig;
+    if (rc == GX_OK && sc && max_hits) {   // the counts and the offsets first, then the exact capacity
+        t0 = std::chrono::steady_clock::now();
+        xhits.resize((size_t)hoff[npat] + 1);
+        coff.assign((size_t)hoff[npat] + 1, 0);
+        rc = gx_suffix_index_extend(idx, packed.data(), off.data(), npat, hoff.data(), sta.data(), pos.data(), sc,
+                                    (uint32_t)kedit, xhits.data(), nullptr, 0, coff.data());
+        if (rc == GX_OK) {
+            cig.resize((size_t)coff.back() + 1);
+            rc = gx_suffix_index_extend(idx, packed.data(), off.data(), npat, hoff.data(), sta.data(), pos.data(), sc,
+                                        (uint32_t)kedit, xhits.data(), cig.data(), cig.size(), coff.data());
+        }
+        const auto xus = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+        if (rc == GX_OK && info) {
+            uint64_t xh = 0, cells = 0, tb = 0, chunks = 0;
+            double fms = 0, wms = 0;
+            gx_extend_info(ctx, &xh, &cells, &tb, &chunks, &fms, &wms);
+            fprintf(stderr, "[INFO] %llu hits aligned on the band of %d in %lld us (%llu cell updates, %llu trace bytes in %llu "
+                            "chunks, fill %.3f ms, walk %.3f ms)\n",
+                    (unsigned long long)xh, kedit, (long long)xus, (unsigned long long)cells, (unsigned long long)tb,
+                    (unsigned long long)chunks, fms, wms);
+        }
+    }
     if (rc == GX_OK && info && kedit >= 0) {
         uint64_t cands = 0, pre = 0, cells = 0;
         double sms = 0, vms = 0, dms = 0;
@@ -549,8 +579,12 @@ int run_search(const std::string& fasta, const std::string& patterns, uint32_t m
         if (kedit >= 0) {   // name, length, count, best_dist, best_end, start-end:dist triples
             fprintf(f, "%s\t%llu\t%u\t%u\t%u\t", q.name(p).c_str(), (unsigned long long)q.sl[p], ehits[p].count,
                     ehits[p].best_dist, ehits[p].best_end);
-            for (uint64_t k = hoff[p]; k < hoff[p + 1]; ++k)
+            for (uint64_t k = hoff[p]; k < hoff[p + 1]; ++k) {
                 fprintf(f, k == hoff[p] ? "%u-%u:%u" : ",%u-%u:%u", sta[k], pos[k], (unsigned)dst[k]);
+                if (xhits.empty()) continue;
+                fprintf(f, ":%d:", xhits[k].score);   // start-end:dist:score:CIGAR
+                for (uint64_t r = coff[k]; r < coff[k + 1]; ++r) fprintf(f, "%u%c", cig[r] >> 4, "MID?"[cig[r] & 3u]);
+            }
         } else if (exact) {
             fprintf(f, "%s\t%llu\t%u\t%u\t%u\t", q.name(p).c_str(), (unsigned long long)q.sl[p], hits[p].count,
                     hits[p].prefix_len, hits[p].prefix_pos);
@@ -630,7 +664,7 @@ int main(int argc, char** argv) {
     std::string config = "config.toml", type, fasta, dir, tsv = "similarity_matrix.tsv", mode, patterns;
     int ngpu = 0;
     long long max_hits = 16, kmis = -1, kedit = -1, mem_len = -1;
-    bool with_self = true, stats = false, out_set = false;
+    bool with_self = true, stats = false, out_set = false, cigar = false;
     for (int k = 1; k < argc; ++k) {
         std::string a = argv[k];
         auto next = [&](std::string& dst) {
@@ -648,6 +682,7 @@ int main(int argc, char** argv) {
         else if (a == "--max-hits") { std::string v; next(v); max_hits = atoll(v.c_str()); }
         else if (a == "-k" || a == "--mismatches") { std::string v; next(v); kmis = atoll(v.c_str()); if (kmis < 0) { usage(); return 2; } }
         else if (a == "-e" || a == "--edits") { std::string v; next(v); kedit = atoll(v.c_str()); if (kedit < 0) { usage(); return 2; } }
+        else if (a == "--cigar") cigar = true;
         else if (a == "--mem") { std::string v; next(v); mem_len = atoll(v.c_str()); if (mem_len < 1 || mem_len > 0xFFFFFFFFll) { usage(); return 2; } }
         else if (a == "--suffix-links") {}   // (the reference's build strategy: no counterpart)
         else if (a == "-g" || a == "--gpus") { std::string v; next(v); ngpu = atoi(v.c_str()); }
@@ -658,19 +693,22 @@ int main(int argc, char** argv) {
     const bool by_file = mode == "align" || mode == "suffix-tree" || mode == "search";
     if (mode.empty() || (by_file && fasta.empty()) || (!by_file && dir.empty()) ||
         (mode == "search" && (patterns.empty() || max_hits < 0 || max_hits > 0xFFFFFFFFll || kmis > 0xFFFF || kedit > 0xFFFF ||
-                              (kmis >= 0 && kedit >= 0) || (mem_len >= 0 && (kmis >= 0 || kedit >= 0))))) {
+                              (kmis >= 0 && kedit >= 0) || (mem_len >= 0 && (kmis >= 0 || kedit >= 0)))) ||
+        (cigar && (mode != "search" || kedit < 0))) {
         usage();
         return 2;
     }
     if (mode == "compare") return run_compare(dir, tsv);   // (reads no scores: main.rs:216-221)
     if (mode == "search" && mem_len >= 0) return run_mems(fasta, patterns, (uint32_t)mem_len, out_set ? tsv : std::string());
-    if (mode == "search") return run_search(fasta, patterns, (uint32_t)max_hits, out_set ? tsv : std::string(), (int)kmis, (int)kedit);
+    if (mode == "search" && !cigar)
+        return run_search(fasta, patterns, (uint32_t)max_hits, out_set ? tsv : std::string(), (int)kmis, (int)kedit, nullptr);
     if (mode == "suffix-tree") return run_suffix_tree(fasta, type, stats, out_set ? tsv : std::string());
     gx_scores sc;
     if (gx_config_load(config.c_str(), &sc) != GX_OK) {
         fprintf(stderr, "[ERROR] %s\n", gx_last_error());
         return 1;  // config.rs: exit(1)
     }
+    if (mode == "search") return run_search(fasta, patterns, (uint32_t)max_hits, out_set ? tsv : std::string(), -1, (int)kedit, &sc);
     if (mode == "align") return run_align(sc, type.empty() ? "local" : type, fasta);  // main.rs:35 default "local"
     return run_all_vs_all(sc, type.empty() ? "global" : type, dir, tsv, ngpu, with_self);
 }

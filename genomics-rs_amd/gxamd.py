@@ -99,7 +99,8 @@ EXPORTED = ["gx_last_error", "gx_version", "gx_context_create", "gx_context_dest
             "gx_suffix_index_build", "gx_suffix_index_free", "gx_suffix_index_info", "gx_suffix_index_export",
             "gx_suffix_index_search", "gx_search_info", "gx_suffix_index_search_approx", "gx_approx_info",
             "gx_suffix_index_search_edit", "gx_edit_info",
-            "gx_suffix_index_match_stats", "gx_suffix_index_mems", "gx_match_info"]
+            "gx_suffix_index_match_stats", "gx_suffix_index_mems", "gx_match_info",
+            "gx_suffix_index_extend", "gx_extend_info"]
 
 _lib = None
 
@@ -205,6 +206,8 @@ def lib():
     L.gx_suffix_index_match_stats.argtypes = [vp, vp, vp, sz, ctypes.c_uint32, vp]
     L.gx_suffix_index_mems.argtypes = [vp, vp, vp, sz, ctypes.c_uint32, vp, sz, vp, vp]
     L.gx_match_info.argtypes = [vp, u64p, u64p, u64p, dp, dp, dp]
+    L.gx_suffix_index_extend.argtypes = [vp, vp, vp, sz, vp, vp, vp, ctypes.POINTER(CScores), ctypes.c_uint32, vp, vp, sz, vp]
+    L.gx_extend_info.argtypes = [vp, u64p, u64p, u64p, u64p, dp, dp]
     _lib = L
     return L
 
@@ -1095,11 +1098,18 @@ APPROX_HIT_DTYPE = np.dtype([("count", "<u4"), ("best_dist", "<u4"), ("best_pos"
 EDIT_HIT_DTYPE = np.dtype([("count", "<u4"), ("best_dist", "<u4"), ("best_end", "<u4"), ("candidates", "<u4")])
 MATCH_STAT_DTYPE = np.dtype([("len", "<u4"), ("lo", "<u4"), ("count", "<u4"), ("pos", "<u4")])
 MEM_DTYPE = np.dtype([("qpos", "<u4"), ("tpos", "<u4"), ("len", "<u4")])
+EXTEND_HIT_DTYPE = np.dtype([("score", "<i4"), ("n_steps", "<u4"), ("matches", "<u4"), ("mismatches", "<u4"),
+                             ("opening_gaps", "<u4"), ("gap_extensions", "<u4"), ("identities", "<u4"),
+                             ("cigar_len", "<u4")])
+EXTEND_MAX_BAND = 15        # GX_EXTEND_MAX_BAND
+EXTEND_MAX_SCORE = 32767    # GX_EXTEND_MAX_SCORE
+CIGAR_OPS = "MID"           # a run is len << 4 | op
 APPROX_MAX_K = 8        # GX_APPROX_MAX_K
 EDIT_MAX_M = 4096       # GX_EDIT_MAX_M
 NO_DIST = 0xFFFFFFFF    # best_dist of a pattern without an occurrence
 ALL_HITS = 0xFFFFFFFF   # max_hits: every occurrence
 _FIRST_CAP = 1 << 22    # positions asked for before the count is known (GX_ECAP names the rest)
+_FIRST_RUNS = 8         # CIGAR runs a hit asked for before the count is known: a hit within three edits has at most seven
 
 
 class SuffixIndex:
@@ -1275,6 +1285,60 @@ class SuffixIndex:
         return {"qpos": np.ascontiguousarray(mem["qpos"]), "tpos": np.ascontiguousarray(mem["tpos"]),
                 "length": np.ascontiguousarray(mem["len"]), "mem_offsets": moff, "candidates": cand}
 
+    def extend(self, reads, hits, scores: Optional["Scores"] = None, band: Optional[int] = None,
+               cigars: bool = True) -> dict:
+        """gx_suffix_index_extend: the reference's global alignment (alignment_table, then retrace) of every
+        hit's window s[start:end] (s1) with its read (s2) on the cells |j - i| <= band.  `reads` as `patterns`
+        of search; `hits` is a search_edit result or any mapping with "hit_offsets", "starts" and "ends"
+        (read p's hits at hit_offsets[p]:hit_offsets[p + 1]).  band=None takes the largest |window - read|
+        over the hits (0 <= band <= EXTEND_MAX_BAND).  Returns the record fields as arrays ("score" int32;
+        "n_steps", "matches", "mismatches", "opening_gaps", "gap_extensions", "identities", "cigar_len"
+        uint32, one entry per hit: views of the one record array the call filled, which a batch of millions
+        of hits would take longer to take apart than to align), "cigar_offsets" (uint64, hits + 1) and, with
+        cigars, "cigar" (uint32
+        runs len << 4 | op, M = 0, I = 1, D = 2, in read order; hit h's at cigar_offsets[h]:cigar_offsets[h + 1];
+        None with cigars=False)."""
+        packed, off, npat = self._batch(reads)
+        hoff = np.ascontiguousarray(hits["hit_offsets"], np.uint64)
+        sta = np.ascontiguousarray(hits["starts"], np.uint32)
+        end = np.ascontiguousarray(hits["ends"], np.uint32)
+        if hoff.size != npat + 1:
+            raise GxError(1, f"hit_offsets has {hoff.size} entries for {npat} reads")
+        nh = int(hoff[-1])
+        if sta.size < nh or end.size < nh:
+            raise GxError(1, f"starts and ends have {sta.size} and {end.size} entries for {nh} hits")
+        if band is None:
+            m = np.repeat(np.diff(off).astype(np.int64), np.diff(hoff).astype(np.int64)) if nh else np.zeros(0, np.int64)
+            band = int(np.abs(end[:nh].astype(np.int64) - sta[:nh].astype(np.int64) - m).max()) if nh else 0
+        sc = (scores or Scores()).c()
+        out = np.zeros(max(nh, 1), EXTEND_HIT_DTYPE)
+        coff = np.zeros(nh + 1, np.uint64)
+        cig = None
+
+        def call(cap):
+            nonlocal cig
+            cig = np.zeros(max(cap, 1), np.uint32) if cigars else None
+            return lib().gx_suffix_index_extend(self.ptr, packed.ctypes.data, off.ctypes.data, npat, hoff.ctypes.data,
+                                                sta.ctypes.data, end.ctypes.data, ctypes.byref(sc), band,
+                                                out.ctypes.data, cig.ctypes.data if cigars else None, cap,
+                                                coff.ctypes.data)
+
+        rc = call(_FIRST_RUNS * nh)
+        if rc == 7:
+            rc = call(int(coff[-1]))   # GX_ECAP: cigar_offsets is complete; allocate and repeat
+        _check(rc)
+        r = {f: out[f][:nh] for f in EXTEND_HIT_DTYPE.names}
+        r["cigar_offsets"] = coff
+        r["cigar"] = cig[:int(coff[-1])] if cigars else None
+        return r
+
+    def map_reads(self, reads, k: int, max_hits: int = 16, scores: Optional["Scores"] = None,
+                  band: Optional[int] = None) -> Tuple[dict, dict]:
+        """search_edit(reads, k, max_hits) with starts, then extend of what it reports (band=None: k).
+        Returns both results."""
+        found = self.search_edit(reads, k, max_hits, starts=True)
+        return found, self.extend(reads, found, scores, k if band is None else band)
+
     def sa(self) -> np.ndarray:
         """The suffix array, n + 1 entries (gx_suffix_index_export)."""
         a = np.zeros(self.n + 1, np.uint32)
@@ -1328,6 +1392,23 @@ def edit_info(ctx: Optional["Context"] = None) -> dict:
     _check(lib().gx_edit_info(ctx.ptr, *[ctypes.byref(x) for x in v + ms]))
     return {"candidates": v[0].value, "pre_dedupe_ends": v[1].value, "cell_updates": v[2].value,
             "seed_ms": ms[0].value, "verify_ms": ms[1].value, "dedupe_ms": ms[2].value}
+
+
+def extend_info(ctx: Optional["Context"] = None) -> dict:
+    """gx_extend_info of the last extend on ctx: its hits, cell updates of the fill, the trace bytes of its
+    largest launch, its launches (GX_EXTEND_TRACE_BYTES bounds one), device ms of the fill and of walk, scan
+    and emit."""
+    ctx = ctx or default_context()
+    v = [ctypes.c_uint64() for _ in range(4)]
+    ms = [ctypes.c_double() for _ in range(2)]
+    _check(lib().gx_extend_info(ctx.ptr, *[ctypes.byref(x) for x in v + ms]))
+    return {"hits": v[0].value, "cell_updates": v[1].value, "trace_bytes": v[2].value, "chunks": v[3].value,
+            "fill_ms": ms[0].value, "walk_ms": ms[1].value}
+
+
+def cigar_string(cigar_slice) -> str:
+    """The text of a hit's runs: cigar_string(r["cigar"][o[h]:o[h + 1]]) is e.g. "57M1I42M"."""
+    return "".join(f"{int(x) >> 4}{CIGAR_OPS[int(x) & 15]}" for x in cigar_slice)
 
 
 def match_info(ctx: Optional["Context"] = None) -> dict:

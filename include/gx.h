@@ -678,6 +678,58 @@ int  gx_suffix_index_mems(gx_suffix_index* idx, const uint8_t* queries, const ui
 int  gx_match_info(const gx_context* ctx, uint64_t* candidates, uint64_t* kept, uint64_t* word_compares,
                    double* stats_ms, double* seed_ms, double* emit_ms);
 
+/* ---- banded affine-gap alignment and CIGARs of reported hits --
+ * A hit is (p, b, e): pattern P_p of m bytes and the window s[b .. e) of
+ * w = e - b bytes, 0 <= b <= e <= n.  For each hit the call runs the
+ * reference's global alignment (alignment_table(is_local = false), then retrace,
+ * algo.rs:151-441) with s1 = the window (index i) and s2 = the pattern (index
+ * j), on the cells with |j - i| <= band alone: every plane of a cell outside the
+ * band reads as the reference's negative infinity, the boundary cells (i, 0) and
+ * (0, j) inside it are the reference's.  The retrace starts at (w, m), takes in
+ * every cell the first of S, I, D at the cell's maximum, and labels and counts
+ * its steps as the reference does.  Whenever the reference's own retrace path
+ * stays inside the band, record and steps are the reference's.  Insert and
+ * OpenInsert consume a pattern byte (the CIGAR's I, the read being the query),
+ * Delete and OpenDelete a text byte (D); a diagonal step is an M.
+ *
+ * hit_offsets, starts and ends are what gx_suffix_index_search_edit returns
+ * (npat + 1 offsets; pattern p's hits at [hit_offsets[p], hit_offsets[p + 1])),
+ * or the exact or k-mismatch search's positions with ends = position + m, or the
+ * caller's own.  out[h] is hit h's record.  Its runs, len << 4 | op with M = 0,
+ * I = 1, D = 2, in pattern order, are cigar[cigar_offsets[h] ..
+ * cigar_offsets[h + 1]); cigar = NULL asks for the records and the offsets only.
+ * A host index (ctx = NULL at its build) runs on the host.
+ *
+ * Errors, in this order.  GX_EINVAL: idx, offsets, hit_offsets, scores or
+ * cigar_offsets is NULL; band above GX_EXTEND_MAX_BAND.  GX_ERANGE: a score above
+ * GX_EXTEND_MAX_SCORE in magnitude (int32 is exact below it).
+ * Then the batch checker of the searches (a pattern longer than GX_EDIT_MAX_M:
+ * GX_ERANGE).  GX_EINVAL: hit_offsets does not start at 0 or decreases;
+ * GX_ERANGE: 2^32 hits or more; GX_EINVAL: starts, ends or out is NULL with a
+ * hit; a hit with e < b, e > n or |w - m| > band (hit and pattern named).  After
+ * the run, GX_ERANGE: 2^32 runs or more; GX_ECAP: cigar_cap is below the total
+ * (named): out[] and cigar_offsets[] are complete, cigar[] is untouched. */
+#define GX_EXTEND_MAX_BAND 15
+#define GX_EXTEND_MAX_SCORE 32767
+typedef struct gx_extend_hit {
+    int32_t score; uint32_t n_steps;
+    uint32_t matches, mismatches, opening_gaps, gap_extensions; /* as retrace counts them */
+    uint32_t identities;  /* diagonal steps with s1[i-1] == s2[j-1] */
+    uint32_t cigar_len;   /* runs */
+} gx_extend_hit;
+int  gx_suffix_index_extend(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets /* npat+1 */,
+                            size_t npat, const uint64_t* hit_offsets /* npat+1 */, const uint32_t* starts,
+                            const uint32_t* ends, const gx_scores* scores, uint32_t band,
+                            gx_extend_hit* out /* nhits */, uint32_t* cigar /* may be NULL */, size_t cigar_cap,
+                            uint64_t* cigar_offsets /* nhits+1 */);
+/* The last extend call on ctx: its hits, the cell updates of the fill (the
+ * cells of every hit's table inside the band, at most sum (w + 1)(2 band + 1)),
+ * the bytes of trace of its largest launch, its launches (a batch whose trace
+ * exceeds GX_EXTEND_TRACE_BYTES, read on every call, runs in chunks), and device
+ * time (ms) of the fill and of walk, scan and emit.  Measurement and tests. */
+int  gx_extend_info(const gx_context* ctx, uint64_t* hits, uint64_t* cell_updates, uint64_t* trace_bytes,
+                    uint64_t* chunks, double* fill_ms, double* walk_ms);
+
 #ifdef __cplusplus
 }
 #endif
