@@ -12,6 +12,7 @@
 //   gx_api_search.cpp   search mode: a kept suffix index and batched exact-match and k-mismatch queries on it
 //   gx_api_match.cpp    search mode: matching statistics and maximal exact matches of long queries
 // gx_api_call.h adds the scope of one device call (DevCall, GX_TRY, GX_GET) for the drivers of the last four.
+// gx_api_batch.cpp has the batch pipelines' own scope (BatchScope) and takes GX_TRY from there.
 // Not a public header: host code only, one library.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -277,7 +278,7 @@ struct gx_context {
     int device = 0;
     hipStream_t stream = nullptr;
     hipStream_t cstream = nullptr;   // pipelined path: traceback record copies (D2H) off the fill stream
-    hipStream_t stream2 = nullptr;   // overlapped batches (batch_core_overlap): the second group's fills
+    hipStream_t stream2 = nullptr;   // overlapped batches (pipeline_overlapped): the second group's fills
     hipStream_t tstream = nullptr;   // ... and the walks
     // the three-slot pipeline with the walk on its own stream (which holds a
     // pass's buffers until it is collected): a fill's reductions -- strip

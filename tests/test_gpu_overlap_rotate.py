@@ -1,5 +1,5 @@
 """GPU parity of the rotating overlapped pipeline (gx_api_batch.cpp
-batch_core_overlap, overlap_rotate_plan): a global long-pair batch split in
+pipeline_rotate, overlap_rotate_plan): a global long-pair batch split in
 halves runs its fills i = 2 pass + group through three plane buffers in
 rotation, each group walked on its own behind its fill; fill i reuses the
 buffers of fill i - 3 once the host has collected that fill and its stream has
@@ -9,7 +9,10 @@ oracle's, over enough passes for the three jobs, the four fill slots and the
 six walk slots to wrap out of phase, with unequal groups, with launches that
 share the device, and with two alternating pair sets (a walk that read a
 refilled buffer then gives a wrong alignment, not an equal one).  Local
-batches and GX_OVERLAP_ROTATE=0 keep the two-buffer scheme."""
+batches and GX_OVERLAP_ROTATE=0 keep the two-buffer scheme.  A batch the
+overlapped schemes refuse falls back to the plain pipeline of its kind with
+every pass's checksums in place, and each pipeline leaves the context's slots,
+held buffers and streams fit for the next one."""
 import random
 
 import pytest
@@ -58,13 +61,14 @@ def _got(r):
     return (r.score, r.matches, r.mismatches, r.gap_extensions, r.opening_gaps, r.n_steps)
 
 
-def _run_check(gx, ctx, oracle, pairs, K, scheme, local=False):
-    """K passes of `pairs`: every pass's checksums and results, the last pass's alignments."""
+def _run_check(gx, ctx, oracle, pairs, K, scheme, local=False, twin=1):
+    """K passes of `pairs`: every pass's checksums and results, the last pass's alignments.
+    scheme 0: the plain pipeline, one launch a pass; twin: the twin fill ran (fill_info)."""
     st = gx.StagedPairs(pairs, ctx=ctx)
     res, _ = st.run(gx.Scores(*CONFIG_SCORES), local, keep_planes=True, steps=K, plane_sums=True)
     info = ctx.fill_info()
     # (one pass alone runs unpipelined: one launch, no scheme)
-    assert info["groups"] == (2 if K >= 2 else 1) and info["twin"] == 1, info
+    assert info["groups"] == (2 if K >= 2 and scheme else 1) and info["twin"] == twin, info
     assert ctx.overlap_scheme() == (scheme if K >= 2 else 0)
     sums = st.plane_sums()
     passes = st.pass_results()
@@ -103,7 +107,7 @@ def test_interleaved_launches(gx, ctx, oracle, monkeypatch):
 @pytest.mark.parametrize("poison", [False, True], ids=["plain", "poison"])
 def test_stale_buffer_alternating_sets(gx, ctx, oracle, monkeypatch, poison):
     """Two sets of 16 pairs, same shapes and different sequences, alternate
-    pass by pass (GX_STAGED_ALTERNATE, the call that reaches batch_core_overlap's
+    pass by pass (GX_STAGED_ALTERNATE, the call that reaches the pipelines'
     `alt` sets: pass k runs set k % 2, and such a run is one chunk), five
     passes: every buffer, descriptor block and pinned block a fill or walk
     takes last held the other set's data, so a walk that read a buffer already
@@ -172,3 +176,44 @@ def test_local_batch_keeps_two_buffer_scheme(gx, ctx, oracle):
     rng = random.Random(654)
     pairs = [_planted(rng, 1500 + 37 * k, 1200 + 53 * k, 400 + 20 * k) for k in range(16)]
     _run_check(gx, ctx, oracle, pairs, 3, scheme=1, local=True)
+
+
+def _poison(monkeypatch, poison):
+    if poison:
+        monkeypatch.setenv("GX_POOL_POISON", "1")
+    else:
+        monkeypatch.delenv("GX_POOL_POISON", raising=False)
+
+
+@pytest.mark.parametrize("poison", [False, True], ids=["plain", "poison"])
+@pytest.mark.parametrize("local", [False, True], ids=["global", "local"])
+def test_fallback_keeps_every_pass_checksums(gx, ctx, oracle, monkeypatch, poison, local):
+    """GX_OVERLAP=1 asks for the overlapped pipeline and GX_TWIN=0 keeps the
+    fills off the twin fill, so the admission check refuses: a global batch
+    runs the three-slot pipeline, a local one the two-slot pipeline, one
+    launch a pass and no scheme.  The checksums of all four passes are in
+    place: the fallback writes them from where the call's first would go."""
+    monkeypatch.setenv("GX_TWIN", "0")
+    _poison(monkeypatch, poison)
+    _run_check(gx, ctx, oracle, PAIRS20, 4, scheme=0, local=local, twin=0)
+
+
+@pytest.mark.parametrize("poison", [False, True], ids=["plain", "poison"])
+def test_pipelines_back_to_back(gx, ctx, oracle, monkeypatch, poison):
+    """Rotation, the three-slot pipeline, scheme 1, a one-pass batch and the
+    rotation again on one context: each leaves the slots, the held buffers and
+    the streams fit for the next one."""
+    _poison(monkeypatch, poison)
+    _run_check(gx, ctx, oracle, PAIRS20, 4, scheme=2)
+    monkeypatch.setenv("GX_OVERLAP", "0")
+    _run_check(gx, ctx, oracle, PAIRS20, 5, scheme=0)
+    monkeypatch.setenv("GX_OVERLAP", "1")
+    monkeypatch.setenv("GX_OVERLAP_ROTATE", "0")
+    _run_check(gx, ctx, oracle, PAIRS20, 3, scheme=1)
+    batch = gx.align_batch(PAIRS20, gx.Scores(*CONFIG_SCORES), False, ctx=ctx, max_cell=False)
+    for p, ((a, b), (steps, r)) in enumerate(zip(PAIRS20, batch)):
+        o = _ref(oracle, a, b)
+        assert _got(r) == _want(o), p
+        assert _steps_list(steps) == o.alignment(), p
+    monkeypatch.delenv("GX_OVERLAP_ROTATE")
+    _run_check(gx, ctx, oracle, PAIRS20, 3, scheme=2)

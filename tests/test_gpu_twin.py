@@ -365,7 +365,7 @@ def test_twin_auto_selection(gx, ctx, oracle, monkeypatch, kind):
 @pytest.mark.parametrize("launch_env", ["auto", "w4_grid3"])
 def test_twin_overlapped_global(gx, ctx, oracle, monkeypatch, launch_env):
     """The headline's launch shape: a long-pair global batch through the
-    overlapped two-group pipeline (gx_api_batch.cpp batch_core_overlap: group A's
+    overlapped two-group pipeline (gx_api_batch.cpp pipeline_overlapped: group A's
     fill of pass k+1 beside pass k's walk into a second A buffer, group B's
     fill of pass k+1 waiting on the device for pass k's walk before it reuses
     B's buffers).  20 mixed shapes, three passes: every pass's plane

@@ -187,7 +187,7 @@ def test_local_twin_64k_related(gx, ctx, monkeypatch):
 
 def test_local_twin_overlapped(gx, ctx, oracle, monkeypatch):
     """A long-pair local batch (>= 16 pairs, n >= 16,384) takes the overlapped
-    two-group pipeline (gx_api_batch.cpp batch_core_overlap): each pass's walk runs
+    two-group pipeline (gx_api_batch.cpp pipeline_two_buffer): each pass's walk runs
     beside the next pass's fill and reads its start cells (the last maxima,
     finalize_kernel's PairRes) on the device.  Three passes, every result of
     every pass against the oracle."""

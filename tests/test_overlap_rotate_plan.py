@@ -1,6 +1,6 @@
 """CPU: the index arithmetic of the rotating overlapped pipeline
 (gx_api_batch.cpp overlap_rotate_plan, exported as gx_overlap_rotate_plan; the
-driver batch_core_overlap calls the same function).  Fill i = 2 pass + group
+driver pipeline_rotate calls the same function).  Fill i = 2 pass + group
 takes FillJob i % 3, a fill slot, a walk slot and a stream; its stream waits
 on the device for one earlier walk; and the host has collected some fills and
 labelled some walks before it enqueues fill i.  Replaying the driver's enqueue

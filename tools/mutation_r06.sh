@@ -1,4 +1,4 @@
-# Mutation builds of the three-slot short-batch pipeline (gx_api_batch.cpp trace_dev):
+# Mutation builds of the three-slot short-batch pipeline (gx_api_batch.cpp pipeline_three_slot, trace_dev):
 #   mut_nowait: no hipStreamWaitEvent(tstream, fdone) before the walk on its own stream
 #   mut_early:  the fill's buffers go back to the pool as soon as the walk is queued
 # Each must fail tests/test_gpu_atsize.py::test_short_pipeline_alternating_sets (exit 1 = tests failed).

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Mutation check of the rotating overlapped pipeline's stream order
-# (gx_api_batch.cpp batch_core_overlap): builds
+# (gx_api_batch.cpp pipeline_rotate): builds
 # genomics-rs_amd/build_var/libgx_amd_rotate_nowait.so from the current
 # objects with gx_api_batch.cpp compiled under -DGX_MUT_NO_ROTATE_WAIT
 # (fill i's stream then no longer waits for walk i - 3, the last reader of the
