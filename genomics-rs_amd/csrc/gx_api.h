@@ -11,7 +11,9 @@
 //   gx_api_suffix.cpp   suffix-tree mode: BWT and tree statistics from the suffix array (main.rs:154-215)
 //   gx_api_search.cpp   search mode: a kept suffix index and batched exact-match and k-mismatch queries on it
 //   gx_api_match.cpp    search mode: matching statistics and maximal exact matches of long queries
-// gx_api_call.h adds the scope of one device call (DevCall, GX_TRY, GX_GET) for the drivers of the last four.
+//   gx_api_extend.cpp   search mode: banded affine-gap alignment and CIGARs of reported hits
+//   gx_api_chain.cpp    search mode: colinear chains of a long query's anchors
+// gx_api_call.h adds the scope of one device call (DevCall, GX_TRY, GX_GET) for the drivers of the last six.
 // gx_api_batch.cpp has the batch pipelines' own scope (BatchScope) and takes GX_TRY from there.
 // Not a public header: host code only, one library.
 #pragma once
@@ -373,6 +375,9 @@ struct gx_context {
     // the last extend call (gx_extend_info; gx_api_extend.cpp)
     uint64_t ext_hits = 0, ext_cells = 0, ext_trace_bytes = 0, ext_chunks = 0;
     double ext_fill_ms = 0.0, ext_walk_ms = 0.0;
+    // the last chain call (gx_chain_info; gx_api_chain.cpp)
+    uint64_t chn_anchors = 0, chn_segments = 0, chn_evals = 0, chn_chains = 0;
+    double chn_score_ms = 0.0, chn_chain_ms = 0.0;
 };
 
 // search mode's index (gx_api_search.cpp builds and frees it; gx_api_match.cpp reads it)

@@ -62,6 +62,13 @@
 //       (gx_suffix_index_mems).  One line per MEM: query name,
 //       qpos, tpos, len (0-based), by query, then qpos, then tpos; after them
 //       one line per query without a MEM: name, -, -, 0.
+//   gx-align search ... --mem L --chain [--chain-gap G] [--chain-drift D] [--chain-pred H] [--chain-min-score S]
+//       The MEMs of every query chained into colinear chains (gx_chain_anchors,
+//       DESIGN.md 23; max_gap, max_drift, max_pred and min_score, the library's
+//       defaults where not given).  One line per chain instead of the MEMs:
+//       query name, chain number within the query, score, n_anchors, qstart,
+//       qend, tstart, tend; after them one line per query without a chain:
+//       name, -, 0.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -88,7 +95,8 @@ void usage() {
             "       gx-align suffix-tree -f|--fasta-path <FASTA> [-a|--alphabet-file <ALPHABET>] [--suffix-links] "
             "[--stats] [-o <BWT>]\n"
             "       gx-align search -f|--fasta-path <GENOME> -p|--patterns <PATTERNS> [--max-hits <K>] [-k <MISMATCHES> | -e <EDITS> [--cigar]] [-o <TSV>]\n"
-            "       gx-align search -f|--fasta-path <GENOME> -p|--patterns <QUERIES> --mem <MIN_LEN> [-o <TSV>]\n");
+            "       gx-align search -f|--fasta-path <GENOME> -p|--patterns <QUERIES> --mem <MIN_LEN> [--chain [--chain-gap <G>] "
+            "[--chain-drift <D>] [--chain-pred <H>] [--chain-min-score <S>]] [-o <TSV>]\n");
 }
 
 struct Records {
@@ -602,7 +610,9 @@ int run_search(const std::string& fasta, const std::string& patterns, uint32_t m
 }
 
 // search --mem L on GPU 0: the MEMs of every record of the query file against the genome's first record.
-int run_mems(const std::string& fasta, const std::string& queries, uint32_t min_len, const std::string& out_path) {
+// chain: with --chain, the parameters of gx_chain_anchors on those MEMs; the file then holds the chains.
+int run_mems(const std::string& fasta, const std::string& queries, uint32_t min_len, const std::string& out_path,
+             const gx_chain_params* chain) {
     const char* lg = getenv("GX_LOG");
     const bool info = lg && (!strcmp(lg, "info") || !strcmp(lg, "debug"));
     if (info) fprintf(stderr, "[INFO] MODE: Search (MEMs)\n[INFO] Loading sequences from %s and %s\n", fasta.c_str(), queries.c_str());
@@ -643,10 +653,49 @@ int run_mems(const std::string& fasta, const std::string& queries, uint32_t min_
                 (unsigned long long)cands, (unsigned long long)kept, (unsigned long long)words, sms, ems);
     }
     gx_suffix_index_free(idx);
+    // --chain: one call, since chains and members are at most the anchors; above 2^22 anchors that many are
+    // asked for first, and a GX_ECAP, which leaves the totals, is answered with the exact capacities
+    std::vector<gx_chain> chains;
+    std::vector<uint32_t> members;
+    std::vector<uint64_t> coff(nq + 1, 0);
+    const int mems_rc = rc;
+    if (rc == GX_OK && chain) {
+        uint64_t mtot = 0;
+        t0 = std::chrono::steady_clock::now();
+        chains.resize(std::min<size_t>(std::max<size_t>(mems.size(), 1), (size_t)1 << 22));
+        members.resize(chains.size());
+        for (int attempt = 0; attempt < 2; ++attempt) {
+            rc = gx_chain_anchors(ctx, mems.data(), moff.data(), nq, chain, nullptr, nullptr, chains.data(), chains.size(),
+                                  members.data(), members.size(), coff.data(), &mtot);
+            if (rc != GX_ECAP) break;
+            chains.resize((size_t)coff[nq]);
+            members.resize((size_t)mtot);
+        }
+        const auto cus = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
+        if (rc == GX_OK && info) {
+            uint64_t an = 0, segs = 0, evals = 0, nch = 0;
+            double sms = 0, cms = 0;
+            gx_chain_info(ctx, &an, &segs, &evals, &nch, &sms, &cms);
+            fprintf(stderr, "[INFO] %llu anchors in %llu segments chained in %lld us (%llu pair evaluations, %llu chains, "
+                            "score %.3f ms, chains %.3f ms)\n",
+                    (unsigned long long)an, (unsigned long long)segs, (long long)cus, (unsigned long long)evals,
+                    (unsigned long long)nch, sms, cms);
+        }
+    }
     gx_context_destroy(ctx);
-    if (rc != GX_OK) return fail_msg("search --mem", rc);
+    if (rc != GX_OK) return fail_msg(mems_rc != GX_OK ? "search --mem" : "search --chain", rc);
     FILE* f = out_path.empty() ? stdout : fopen(out_path.c_str(), "w");
     if (!f) { fprintf(stderr, "[ERROR] cannot write %s\n", out_path.c_str()); return 1; }
+    if (chain) {
+        for (size_t c = 0; c < nq; ++c)
+            for (uint64_t k = coff[c]; k < coff[c + 1]; ++k)
+                fprintf(f, "%s\t%llu\t%d\t%u\t%u\t%u\t%u\t%u\n", q.name(c).c_str(), (unsigned long long)(k - coff[c]),
+                        chains[k].score, chains[k].n_anchors, chains[k].qstart, chains[k].qend, chains[k].tstart, chains[k].tend);
+        for (size_t c = 0; c < nq; ++c)
+            if (coff[c + 1] == coff[c]) fprintf(f, "%s\t-\t0\n", q.name(c).c_str());
+        if (f != stdout) fclose(f);
+        return 0;
+    }
     for (size_t c = 0; c < nq; ++c)
         for (uint64_t k = moff[c]; k < moff[c + 1]; ++k)
             fprintf(f, "%s\t%u\t%u\t%u\n", q.name(c).c_str(), mems[k].qpos, mems[k].tpos, mems[k].len);
@@ -664,7 +713,16 @@ int main(int argc, char** argv) {
     std::string config = "config.toml", type, fasta, dir, tsv = "similarity_matrix.tsv", mode, patterns;
     int ngpu = 0;
     long long max_hits = 16, kmis = -1, kedit = -1, mem_len = -1;
-    bool with_self = true, stats = false, out_set = false, cigar = false;
+    bool with_self = true, stats = false, out_set = false, cigar = false, chain = false, chain_opt = false;
+    gx_chain_params cp{GX_CHAIN_DEFAULT_W_MATCH,  GX_CHAIN_DEFAULT_W_DRIFT,  GX_CHAIN_DEFAULT_MAX_GAP,
+                       GX_CHAIN_DEFAULT_MAX_DRIFT, GX_CHAIN_DEFAULT_MAX_PRED, GX_CHAIN_DEFAULT_MIN_SCORE};
+    // a chain parameter's number: the library holds it to its range
+    auto chain_num = [&](long long& dst, const std::string& v) {
+        char* end = nullptr;
+        dst = strtoll(v.c_str(), &end, 10);
+        chain_opt = true;
+        return end != v.c_str() && !*end && dst >= 0 && dst <= 0x7FFFFFFFll;
+    };
     for (int k = 1; k < argc; ++k) {
         std::string a = argv[k];
         auto next = [&](std::string& dst) {
@@ -684,6 +742,17 @@ int main(int argc, char** argv) {
         else if (a == "-e" || a == "--edits") { std::string v; next(v); kedit = atoll(v.c_str()); if (kedit < 0) { usage(); return 2; } }
         else if (a == "--cigar") cigar = true;
         else if (a == "--mem") { std::string v; next(v); mem_len = atoll(v.c_str()); if (mem_len < 1 || mem_len > 0xFFFFFFFFll) { usage(); return 2; } }
+        else if (a == "--chain") chain = true;
+        else if (a == "--chain-gap" || a == "--chain-drift" || a == "--chain-pred" || a == "--chain-min-score") {
+            std::string v;
+            long long x = 0;
+            next(v);
+            if (!chain_num(x, v)) { usage(); return 2; }
+            if (a == "--chain-gap") cp.max_gap = (uint32_t)x;
+            else if (a == "--chain-drift") cp.max_drift = (uint32_t)x;
+            else if (a == "--chain-pred") cp.max_pred = (uint32_t)x;
+            else cp.min_score = (int32_t)x;
+        }
         else if (a == "--suffix-links") {}   // (the reference's build strategy: no counterpart)
         else if (a == "-g" || a == "--gpus") { std::string v; next(v); ngpu = atoi(v.c_str()); }
         else if (a == "--no-self") with_self = false;
@@ -694,12 +763,12 @@ int main(int argc, char** argv) {
     if (mode.empty() || (by_file && fasta.empty()) || (!by_file && dir.empty()) ||
         (mode == "search" && (patterns.empty() || max_hits < 0 || max_hits > 0xFFFFFFFFll || kmis > 0xFFFF || kedit > 0xFFFF ||
                               (kmis >= 0 && kedit >= 0) || (mem_len >= 0 && (kmis >= 0 || kedit >= 0)))) ||
-        (cigar && (mode != "search" || kedit < 0))) {
+        (cigar && (mode != "search" || kedit < 0)) || (chain && (mode != "search" || mem_len < 0)) || (chain_opt && !chain)) {
         usage();
         return 2;
     }
     if (mode == "compare") return run_compare(dir, tsv);   // (reads no scores: main.rs:216-221)
-    if (mode == "search" && mem_len >= 0) return run_mems(fasta, patterns, (uint32_t)mem_len, out_set ? tsv : std::string());
+    if (mode == "search" && mem_len >= 0) return run_mems(fasta, patterns, (uint32_t)mem_len, out_set ? tsv : std::string(), chain ? &cp : nullptr);
     if (mode == "search" && !cigar)
         return run_search(fasta, patterns, (uint32_t)max_hits, out_set ? tsv : std::string(), (int)kmis, (int)kedit, nullptr);
     if (mode == "suffix-tree") return run_suffix_tree(fasta, type, stats, out_set ? tsv : std::string());

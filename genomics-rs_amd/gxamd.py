@@ -100,7 +100,8 @@ EXPORTED = ["gx_last_error", "gx_version", "gx_context_create", "gx_context_dest
             "gx_suffix_index_search", "gx_search_info", "gx_suffix_index_search_approx", "gx_approx_info",
             "gx_suffix_index_search_edit", "gx_edit_info",
             "gx_suffix_index_match_stats", "gx_suffix_index_mems", "gx_match_info",
-            "gx_suffix_index_extend", "gx_extend_info"]
+            "gx_suffix_index_extend", "gx_extend_info",
+            "gx_chain_anchors", "gx_chain_info"]
 
 _lib = None
 
@@ -208,6 +209,8 @@ def lib():
     L.gx_match_info.argtypes = [vp, u64p, u64p, u64p, dp, dp, dp]
     L.gx_suffix_index_extend.argtypes = [vp, vp, vp, sz, vp, vp, vp, ctypes.POINTER(CScores), ctypes.c_uint32, vp, vp, sz, vp]
     L.gx_extend_info.argtypes = [vp, u64p, u64p, u64p, u64p, dp, dp]
+    L.gx_chain_anchors.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp]
+    L.gx_chain_info.argtypes = [vp, u64p, u64p, u64p, u64p, dp, dp]
     _lib = L
     return L
 
@@ -1101,6 +1104,12 @@ MEM_DTYPE = np.dtype([("qpos", "<u4"), ("tpos", "<u4"), ("len", "<u4")])
 EXTEND_HIT_DTYPE = np.dtype([("score", "<i4"), ("n_steps", "<u4"), ("matches", "<u4"), ("mismatches", "<u4"),
                              ("opening_gaps", "<u4"), ("gap_extensions", "<u4"), ("identities", "<u4"),
                              ("cigar_len", "<u4")])
+CHAIN_DTYPE = np.dtype([("member_off", "<u8"), ("score", "<i4"), ("n_anchors", "<u4"), ("root", "<u4"), ("end", "<u4"),
+                        ("qstart", "<u4"), ("tstart", "<u4"), ("qend", "<u4"), ("tend", "<u4")])
+CHAIN_NONE = 0xFFFFFFFF     # GX_CHAIN_NONE: pred of a root
+CHAIN_MAX_PRED = 256        # GX_CHAIN_MAX_PRED
+CHAIN_DEFAULTS = {"w_match": 8, "w_drift": 1, "max_gap": 5000, "max_drift": 500, "max_pred": 64,
+                  "min_score": 0}   # GX_CHAIN_DEFAULT_*
 EXTEND_MAX_BAND = 15        # GX_EXTEND_MAX_BAND
 EXTEND_MAX_SCORE = 32767    # GX_EXTEND_MAX_SCORE
 CIGAR_OPS = "MID"           # a run is len << 4 | op
@@ -1285,6 +1294,12 @@ class SuffixIndex:
         return {"qpos": np.ascontiguousarray(mem["qpos"]), "tpos": np.ascontiguousarray(mem["tpos"]),
                 "length": np.ascontiguousarray(mem["len"]), "mem_offsets": moff, "candidates": cand}
 
+    def chain_mems(self, queries, min_len: int, **params) -> dict:
+        """mems(queries, min_len), then chain_anchors on its result where the index lives (the device of a
+        device index, the host solver of a host index): {"mems": the one, "chains": the other}."""
+        m = self.mems(queries, min_len)
+        return {"mems": m, "chains": chain_anchors(m, ctx=self._ctx, host=self._ctx is None, **params)}
+
     def extend(self, reads, hits, scores: Optional["Scores"] = None, band: Optional[int] = None,
                cigars: bool = True) -> dict:
         """gx_suffix_index_extend: the reference's global alignment (alignment_table, then retrace) of every
@@ -1404,6 +1419,74 @@ def extend_info(ctx: Optional["Context"] = None) -> dict:
     _check(lib().gx_extend_info(ctx.ptr, *[ctypes.byref(x) for x in v + ms]))
     return {"hits": v[0].value, "cell_updates": v[1].value, "trace_bytes": v[2].value, "chunks": v[3].value,
             "fill_ms": ms[0].value, "walk_ms": ms[1].value}
+
+
+class CChainParams(ctypes.Structure):
+    _fields_ = [("w_match", ctypes.c_uint32), ("w_drift", ctypes.c_uint32), ("max_gap", ctypes.c_uint32),
+                ("max_drift", ctypes.c_uint32), ("max_pred", ctypes.c_uint32), ("min_score", ctypes.c_int32)]
+
+
+def chain_anchors(anchors, ctx: Optional["Context"] = None, host: bool = False, counts_only: bool = False,
+                  **params) -> dict:
+    """gx_chain_anchors: the anchors of a batch of queries chained into colinear chains.
+    `anchors` is what SuffixIndex.mems returns, or any mapping with uint32 "qpos", "tpos", "length" and the
+    uint64 "mem_offsets" (query c's anchors at mem_offsets[c]:mem_offsets[c + 1], ascending by (qpos, tpos)).
+    params: w_match, w_drift, max_gap, max_drift, max_pred, min_score (CHAIN_DEFAULTS).  host=True runs the
+    host solver (no device).  Returns "score" (int32) and "pred" (uint32, CHAIN_NONE at a root; anchor numbers
+    are within the query) of every anchor, the chains' fields as arrays ("member_off", "score_chain" = the
+    chain's score, "n_anchors", "root", "end", "qstart", "tstart", "qend", "tend"), "members" (uint32) and
+    "chain_offsets" (uint64, nq + 1).  One call: a query's chains and members are at most its anchors, so a
+    capacity of the anchor count always suffices (above 2^22 anchors the first call has that many and a GX_ECAP
+    is answered with a second call at the exact totals, which runs the dynamic programme again).
+    counts_only=True asks for the counts alone (empty chains and members)."""
+    unknown = set(params) - set(CHAIN_DEFAULTS)
+    if unknown:
+        raise TypeError(f"chain_anchors: unknown parameters {sorted(unknown)}")
+    p = CChainParams(**{**CHAIN_DEFAULTS, **params})
+    off = np.ascontiguousarray(anchors["mem_offsets"], np.uint64)
+    nq, A = len(off) - 1, len(anchors["qpos"])
+    an = np.zeros(max(A, 1), MEM_DTYPE)
+    an["qpos"][:A], an["tpos"][:A], an["len"][:A] = anchors["qpos"], anchors["tpos"], anchors["length"]
+    c = None if host else (ctx or default_context())
+    score, pred = np.zeros(max(A, 1), np.int32), np.zeros(max(A, 1), np.uint32)
+    coff, mtot = np.zeros(nq + 1, np.uint64), ctypes.c_uint64()
+
+    def call(ch, mem):
+        return lib().gx_chain_anchors(c.ptr if c else None, an.ctypes.data, off.ctypes.data, nq, ctypes.byref(p),
+                                      score.ctypes.data, pred.ctypes.data, ch.ctypes.data if ch is not None else None,
+                                      len(ch) if ch is not None else 0, mem.ctypes.data if mem is not None else None,
+                                      len(mem) if mem is not None else 0, coff.ctypes.data, ctypes.byref(mtot))
+
+    ch, mem = np.zeros(0, CHAIN_DTYPE), np.zeros(0, np.uint32)
+    if counts_only:
+        _check(call(None, None))
+    else:
+        # chains and members are at most the anchors: one call at that capacity, up to _FIRST_CAP; beyond it a
+        # GX_ECAP leaves the totals, and the second call has exactly them
+        cap = max(1, min(A, _FIRST_CAP))
+        ch, mem = np.zeros(cap, CHAIN_DTYPE), np.zeros(cap, np.uint32)
+        rc = call(ch, mem)
+        if rc == 7:
+            ch, mem = np.zeros(max(1, int(coff[-1])), CHAIN_DTYPE), np.zeros(max(1, int(mtot.value)), np.uint32)
+            rc = call(ch, mem)
+        _check(rc)
+        ch, mem = ch[:int(coff[-1])], np.ascontiguousarray(mem[:int(mtot.value)])
+    r = {"score": score[:A], "pred": pred[:A], "members": mem, "chain_offsets": coff, "members_total": int(mtot.value)}
+    for f in CHAIN_DTYPE.names:
+        r["score_chain" if f == "score" else f] = np.ascontiguousarray(ch[f])
+    return r
+
+
+def chain_info(ctx: Optional["Context"] = None) -> dict:
+    """gx_chain_info of the last chain call on ctx: its anchors, segments, the pairs the score kernel
+    evaluated, its reported chains, device ms of flags, scan and score and of best, heads, scans and walk
+    (0 for what did not run)."""
+    ctx = ctx or default_context()
+    v = [ctypes.c_uint64() for _ in range(4)]
+    ms = [ctypes.c_double() for _ in range(2)]
+    _check(lib().gx_chain_info(ctx.ptr, *[ctypes.byref(x) for x in v + ms]))
+    return {"anchors": v[0].value, "segments": v[1].value, "pair_evals": v[2].value, "chains": v[3].value,
+            "score_ms": ms[0].value, "chain_ms": ms[1].value}
 
 
 def cigar_string(cigar_slice) -> str:

@@ -730,6 +730,80 @@ int  gx_suffix_index_extend(gx_suffix_index* idx, const uint8_t* patterns, const
 int  gx_extend_info(const gx_context* ctx, uint64_t* hits, uint64_t* cell_updates, uint64_t* trace_bytes,
                     uint64_t* chunks, double* fill_ms, double* walk_ms);
 
+/* ---- colinear chains of a long query's anchors -----------------
+ * A batch of nq queries' anchors: query c's are anchors[anchor_offsets[c] ..
+ * anchor_offsets[c + 1]), strictly ascending by (qpos, tpos) within a query,
+ * which is the order gx_suffix_index_mems writes.  The call reads no text and no
+ * index: an anchor need not be a match.  Indices below are anchor numbers within
+ * the query, from 0.
+ *
+ * For anchors a < b of one query, dq = q_b - q_a and dt = t_b - t_a (signed):
+ *   a is eligible for b iff b - a <= max_pred, 1 <= dq <= max_gap,
+ *     1 <= dt <= max_gap and |dq - dt| <= max_drift
+ *   ext(a, b) = f(a) + w_match min(len_b, dq, dt) - w_drift |dq - dt|
+ *   f(b) = max(w_match len_b, max over eligible a of ext(a, b))
+ *   pred(b) = the eligible a at that maximum, the largest a among equal ext, and
+ *     only where the maximum is strictly above w_match len_b; GX_CHAIN_NONE
+ *     otherwise, and b is a root.
+ * pred makes a forest.  Every tree gives at most one chain: its end e is the
+ * tree's anchor of largest f (the smallest index among equals), the chain is the
+ * path from the root to e, and it is reported iff f(e) >= min_score.  A query's
+ * chains are disjoint and ordered by root.  members[member_off .. member_off +
+ * n_anchors) of a chain are its anchor numbers ascending; the members of
+ * successive chains follow each other in chain order.  Query c's chains are
+ * chains[chain_offsets[c] .. chain_offsets[c + 1]).
+ *
+ * ctx = NULL runs the host solver, with the same results field by field.
+ * scores[] and preds[] (f and pred of every anchor; either may be NULL) are in
+ * the order of anchors[].  chains = NULL asks for the counts only.
+ *
+ * Errors, in this order.  GX_EINVAL: anchor_offsets, chain_offsets or
+ * members_total is NULL; a parameter out of range (named).  GX_ERANGE: 2^32 - 2049
+ * queries or more.  GX_EINVAL: anchor_offsets does not start at 0 or decreases;
+ * members NULL with chains.  GX_ERANGE: more anchors than GX_APPROX_CAND_BUDGET
+ * (read on every call; up to 100 pooled device bytes an anchor).  GX_EINVAL:
+ * anchors NULL with an anchor.
+ * Then per anchor in turn: GX_EINVAL len = 0; GX_ERANGE qpos + len or tpos + len
+ * at or above 2^32; GX_EINVAL an anchor not above its predecessor in (qpos, tpos)
+ * (query and anchor named); and at a query's end GX_ERANGE w_match sum(len) at or
+ * above 2^31 (query named).  Nothing runs in these cases.  After the run GX_ECAP:
+ * chains_cap, then members_cap, below the total (named): chain_offsets,
+ * members_total, scores and preds are complete, chains and members untouched. */
+#define GX_CHAIN_NONE 0xFFFFFFFFu
+#define GX_CHAIN_MAX_PRED 256
+#define GX_CHAIN_MAX_WEIGHT 1024
+#define GX_CHAIN_MAX_GAP (1u << 20)
+#define GX_CHAIN_DEFAULT_W_MATCH 8
+#define GX_CHAIN_DEFAULT_W_DRIFT 1
+#define GX_CHAIN_DEFAULT_MAX_GAP 5000
+#define GX_CHAIN_DEFAULT_MAX_DRIFT 500
+#define GX_CHAIN_DEFAULT_MAX_PRED 64
+#define GX_CHAIN_DEFAULT_MIN_SCORE 0
+typedef struct gx_chain_params {
+    uint32_t w_match, w_drift, max_gap, max_drift, max_pred;
+    int32_t min_score;
+} gx_chain_params;
+typedef struct gx_chain {
+    uint64_t member_off;
+    int32_t score;               /* f(end) */
+    uint32_t n_anchors, root, end;
+    uint32_t qstart, tstart;     /* of the root */
+    uint32_t qend, tend;         /* start + len of the end */
+} gx_chain;
+int  gx_chain_anchors(gx_context* ctx /* NULL: host */, const gx_mem* anchors, const uint64_t* anchor_offsets /* nq+1 */,
+                      size_t nq, const gx_chain_params* params /* NULL: the defaults */,
+                      int32_t* scores /* may be NULL */, uint32_t* preds /* may be NULL */,
+                      gx_chain* chains /* may be NULL: counts only */, size_t chains_cap, uint32_t* members,
+                      size_t members_cap, uint64_t* chain_offsets /* nq+1 */, uint64_t* members_total);
+/* The last chain call on ctx: its anchors, segments (a query's anchors are cut
+ * wherever qpos advances by more than max_gap: nothing chains across), the pairs
+ * (a, b) of one segment with 1 <= b - a <= max_pred that the score kernel
+ * evaluated, its reported chains, and device time (ms) of flags, scan and score
+ * and of best, heads, scans and walk.  What did not run is 0.  Measurement and
+ * tests. */
+int  gx_chain_info(const gx_context* ctx, uint64_t* anchors, uint64_t* segments, uint64_t* pair_evals, uint64_t* chains,
+                   double* score_ms, double* chain_ms);
+
 #ifdef __cplusplus
 }
 #endif
