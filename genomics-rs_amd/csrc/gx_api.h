@@ -289,6 +289,7 @@ struct gx_context {
     hipStream_t pstream = nullptr;
     bool post_aside = false;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, ev2 = nullptr;
+    hipEvent_t ev_rc0 = nullptr, ev_rc1 = nullptr;   // around the reverse-complement kernel of a stranded staging (the drivers re-record the three above)
     std::mutex mu;
     std::vector<DevBuf> free_list;
     // staged pairs (bench path)
@@ -375,6 +376,10 @@ struct gx_context {
     // the last extend call (gx_extend_info; gx_api_extend.cpp)
     uint64_t ext_hits = 0, ext_cells = 0, ext_trace_bytes = 0, ext_chunks = 0;
     double ext_fill_ms = 0.0, ext_walk_ms = 0.0;
+    // the last staging of a search-mode call (gx_strand_info; gx_api_search.cpp): its items, the reverse bytes the
+    // kernel wrote, and whether ev_rc0, ev_rc1 hold that kernel's time
+    uint64_t strand_items = 0, strand_rc_bytes = 0;
+    bool strand_timed = false;
     // the last chain call (gx_chain_info; gx_api_chain.cpp)
     uint64_t chn_anchors = 0, chn_segments = 0, chn_evals = 0, chn_chains = 0;
     double chn_score_ms = 0.0, chn_chain_ms = 0.0;
@@ -396,7 +401,9 @@ struct BatchKind {
     uint64_t item_max;    // an item's most bytes (0: any)
     bool positions;       // every byte is a position of the device's 32-bit scans (the long queries' range rule)
 };
-int check_batch(const BatchKind& kind, const uint8_t* bytes, const uint64_t* offsets, size_t n);
+// strands (GX_STRAND_*): besides, where the batch's own 32-bit conditions are held and before a byte is read, the same
+// conditions on its item batch's totals ("strands: ...").
+int check_batch(const BatchKind& kind, const uint8_t* bytes, const uint64_t* offsets, size_t n, uint32_t strands = GX_STRAND_FWD);
 // A checked batch as the drivers take it: offsets in 32 bits, and for a host index the bytes with kSufPad zero
 // bytes behind them (a device index pads on the device).
 struct HostBatch {
@@ -404,6 +411,11 @@ struct HostBatch {
     std::vector<uint8_t> padded;
 };
 void narrow_batch(const gx_suffix_index* idx, const uint8_t* bytes, const uint64_t* offsets, size_t n, HostBatch& b);
+// The same for the item batch of a checked batch on `strands` (gx_strand.h): the item offsets, and
+// for a host index the item bytes.  FWD is narrow_batch.
+void strand_batch(const gx_suffix_index* idx, const uint8_t* bytes, const uint64_t* offsets, size_t n, uint32_t strands,
+                  HostBatch& b);
+int check_strands(uint32_t strands);   // GX_EINVAL unless 1, 2 or 3: the first check of every _strands entry point
 
 struct PairHost {
     const uint8_t* s1;   // original bytes (traceback labels, sequence.rs:113 with rev=false)

@@ -94,5 +94,11 @@ struct StagedBatch {
 // Both sources are pageable: the copies have left them once the stream is synchronised.
 int stage_batch(DevCall& call, const char* what, const uint8_t* src, size_t total_bytes, const uint32_t* offs, uint32_t n,
                 StagedBatch& b);
+// The item batch of the caller's n patterns on the chosen strands (gx_strand.h): the same one
+// host copy of src, the reverse items written behind it (BOTH) or beside it (REV) by the kernel of
+// gx_strand.hip.  offs: the caller's n + 1 offsets (the item offsets begin with them).  FWD is stage_batch.
+// Leaves gx_strand_info's numbers in the context.
+int stage_batch_strands(DevCall& call, const char* what, const uint8_t* src, size_t total_bytes, const uint32_t* offs,
+                        uint32_t n, uint32_t strands, StagedBatch& b);
 
 #pragma GCC visibility pop

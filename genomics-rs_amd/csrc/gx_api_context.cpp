@@ -158,6 +158,8 @@ extern "C" int gx_context_create(int device, gx_context** out) {
     HIPCHK(hipEventCreate(&c->ev0));
     HIPCHK(hipEventCreate(&c->ev1));
     HIPCHK(hipEventCreate(&c->ev2));
+    HIPCHK(hipEventCreate(&c->ev_rc0));
+    HIPCHK(hipEventCreate(&c->ev_rc1));
     // Exercise the copy paths once (device->pinned host of a few MB, host->
     // device, memset): the runtime sets some of them up on first use, which
     // otherwise stalled one later batch's traceback copies by ~8 ms.
@@ -211,6 +213,8 @@ extern "C" void gx_context_destroy(gx_context* ctx) {
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
     if (ctx->ev1) (void)hipEventDestroy(ctx->ev1);
     if (ctx->ev2) (void)hipEventDestroy(ctx->ev2);
+    if (ctx->ev_rc0) (void)hipEventDestroy(ctx->ev_rc0);
+    if (ctx->ev_rc1) (void)hipEventDestroy(ctx->ev_rc1);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->cstream) (void)hipStreamDestroy(ctx->cstream);
     if (ctx->stream2) (void)hipStreamDestroy(ctx->stream2);

@@ -18,6 +18,7 @@
 //            exactly the total of runs
 #include "gx_api_call.h"
 #include "gx_extend.h"
+#include "gx_strand.h"
 
 namespace {
 
@@ -133,10 +134,10 @@ int extend_host(const gx_suffix_index* idx, const uint8_t* pats, const uint64_t*
     return GX_OK;
 }
 
-// pats: the caller's pattern bytes, unpadded; offs: their offsets in 32 bits;
+// pats: the caller's pattern bytes, unpadded; offs, npat: the item batch of those on `strands`, offsets in 32 bits;
 // pid, rows: as check_hits left them.  Takes ctx->mu.
 int extend_device(gx_suffix_index* idx, const uint8_t* pats, size_t total_bytes, const uint32_t* offs, uint32_t npat,
-                  const std::vector<uint32_t>& pid, const std::vector<uint32_t>& rows, const uint32_t* starts,
+                  uint32_t strands, const std::vector<uint32_t>& pid, const std::vector<uint32_t>& rows, const uint32_t* starts,
                   const uint32_t* ends, uint32_t nhits, uint64_t steps_bound, const ExtScores& sc, uint32_t band,
                   gx_extend_hit* out, uint32_t* cigar, size_t cap, uint64_t* cigar_offsets) {
     gx_context* ctx = idx->ctx;
@@ -165,7 +166,7 @@ int extend_device(gx_suffix_index* idx, const uint8_t* pats, size_t total_bytes,
     }
     // counters: [0] cell updates, [1] runs
     StagedBatch b;
-    if (const int rc = stage_batch(call, "extend", pats, total_bytes, offs, npat, b)) return rc;
+    if (const int rc = stage_batch_strands(call, "extend", pats, total_bytes, offs, (uint32_t)strand_sources(npat, strands), strands, b)) return rc;
     const uint64_t dev_cap = cigar ? std::min<uint64_t>(cap, steps_bound) : 0;
     const size_t max_hits = std::min<size_t>(max_waves * 64, nhits);
     uint32_t *d_pid = nullptr, *d_sta = nullptr, *d_end = nullptr, *cnt = nullptr, *tmp = nullptr, *d_cig = nullptr;
@@ -237,10 +238,12 @@ int extend_device(gx_suffix_index* idx, const uint8_t* pats, size_t total_bytes,
 // ---------------------------------------------------------------------------
 // C ABI
 
-extern "C" int gx_suffix_index_extend(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets, size_t npat,
-                                      const uint64_t* hit_offsets, const uint32_t* starts, const uint32_t* ends,
-                                      const gx_scores* scores, uint32_t band, gx_extend_hit* out, uint32_t* cigar,
-                                      size_t cigar_cap, uint64_t* cigar_offsets) {
+extern "C" int gx_suffix_index_extend_strands(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets,
+                                              size_t npat, uint32_t strands, const uint64_t* hit_offsets,
+                                              const uint32_t* starts, const uint32_t* ends, const gx_scores* scores,
+                                              uint32_t band, gx_extend_hit* out, uint32_t* cigar, size_t cigar_cap,
+                                              uint64_t* cigar_offsets) {
+    if (const int src = check_strands(strands)) return src;
     if (!idx) return fail(GX_EINVAL, "idx is NULL");
     if (!offsets) return fail(GX_EINVAL, "offsets is NULL");
     if (!hit_offsets) return fail(GX_EINVAL, "hit_offsets is NULL");
@@ -254,8 +257,22 @@ extern "C" int gx_suffix_index_extend(gx_suffix_index* idx, const uint8_t* patte
         if (sv[q] > kExtMaxScore || sv[q] < -kExtMaxScore)
             return fail(GX_ERANGE, std::string("extend: ") + sn[q] + " is " + std::to_string(sv[q]) +
                                        ", above GX_EXTEND_MAX_SCORE = 32767 in magnitude");
-    const int brc = check_batch(kPatterns, patterns, offsets, npat);
+    const int brc = check_batch(kPatterns, patterns, offsets, npat, strands);
     if (brc != GX_OK) return brc;
+    // from here on the patterns are the items of the caller's batch on `strands`: hit_offsets has
+    // one entry per item and one more, and a hit of a reverse item is aligned against that reverse complement
+    const bool dev = idx->ctx != nullptr;
+    const uint8_t* caller_patterns = patterns;
+    const size_t caller_bytes = (size_t)offsets[npat];
+    HostBatch hb;
+    std::vector<uint64_t> item_offsets;
+    if (dev || strands != GX_STRAND_FWD) strand_batch(idx, patterns, offsets, npat, strands, hb);
+    if (strands != GX_STRAND_FWD) {
+        item_offsets.assign(hb.offs.begin(), hb.offs.end());
+        offsets = item_offsets.data();
+        npat = item_offsets.size() - 1;
+        if (!dev) patterns = hb.padded.data();
+    }
     if (hit_offsets[0] != 0) return fail(GX_EINVAL, "hit_offsets[0] is not 0");
     for (size_t p = 0; p < npat; ++p)
         if (hit_offsets[p + 1] < hit_offsets[p])
@@ -268,7 +285,6 @@ extern "C" int gx_suffix_index_extend(gx_suffix_index* idx, const uint8_t* patte
     if (nhits && !ends) return fail(GX_EINVAL, "ends is NULL");
     if (nhits && !out) return fail(GX_EINVAL, "out is NULL");
     std::vector<uint32_t> pid, rows;
-    const bool dev = idx->ctx != nullptr;
     uint64_t steps_bound = 0;
     const int hrc = check_hits(idx->n, offsets, npat, hit_offsets, starts, ends, band, dev ? &pid : nullptr,
                                dev ? &rows : nullptr, &steps_bound);
@@ -285,10 +301,16 @@ extern "C" int gx_suffix_index_extend(gx_suffix_index* idx, const uint8_t* patte
     const ExtScores sc{(int32_t)sv[0], (int32_t)sv[1], (int32_t)sv[2], (int32_t)sv[3]};
     if (!dev)
         return extend_host(idx, patterns, offsets, npat, hit_offsets, starts, ends, sc, band, out, cigar, cigar_cap, cigar_offsets);
-    HostBatch hb;
-    narrow_batch(idx, patterns, offsets, npat, hb);
-    return extend_device(idx, patterns, (size_t)offsets[npat], hb.offs.data(), (uint32_t)npat, pid, rows, starts, ends,
+    return extend_device(idx, caller_patterns, caller_bytes, hb.offs.data(), (uint32_t)npat, strands, pid, rows, starts, ends,
                          (uint32_t)nhits, steps_bound, sc, band, out, cigar, cigar_cap, cigar_offsets);
+}
+
+extern "C" int gx_suffix_index_extend(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets, size_t npat,
+                                      const uint64_t* hit_offsets, const uint32_t* starts, const uint32_t* ends,
+                                      const gx_scores* scores, uint32_t band, gx_extend_hit* out, uint32_t* cigar,
+                                      size_t cigar_cap, uint64_t* cigar_offsets) {
+    return gx_suffix_index_extend_strands(idx, patterns, offsets, npat, GX_STRAND_FWD, hit_offsets, starts, ends, scores, band, out,
+                                          cigar, cigar_cap, cigar_offsets);
 }
 
 extern "C" int gx_extend_info(const gx_context* ctx, uint64_t* hits, uint64_t* cell_updates, uint64_t* trace_bytes,

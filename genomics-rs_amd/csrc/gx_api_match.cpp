@@ -16,6 +16,7 @@
 // searches use (gx_api.h, gx_api_call.h).
 #include "gx_api_call.h"
 #include "gx_match.h"
+#include "gx_strand.h"
 
 namespace {
 
@@ -99,8 +100,8 @@ int mems_host(const gx_suffix_index* idx, const uint8_t* q, const uint32_t* offs
     return GX_OK;
 }
 
-// q: the caller's npos query bytes, unpadded.  Takes ctx->mu.
-int stats_device(gx_suffix_index* idx, const uint8_t* q, const uint32_t* offs, uint32_t nq, uint32_t W,
+// q: the caller's query bytes, unpadded; offs, nq: the item batch of those on `strands` (npos item bytes).  Takes ctx->mu.
+int stats_device(gx_suffix_index* idx, const uint8_t* q, const uint32_t* offs, uint32_t nq, uint32_t strands, uint32_t W,
                  gx_match_stat* stats) {
     gx_context* ctx = idx->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -111,7 +112,7 @@ int stats_device(gx_suffix_index* idx, const uint8_t* q, const uint32_t* offs, u
     reset_info(ctx);
     if (!npos) return GX_OK;
     StagedBatch b;
-    if (const int rc = stage_batch(call, "match", q, npos, offs, nq, b)) return rc;
+    if (const int rc = stage_batch_strands(call, "match", q, (size_t)strand_sources(npos, strands), offs, (uint32_t)strand_sources(nq, strands), strands, b)) return rc;
     MatchStat* d_stats = nullptr;
     GX_GET(call, d_stats, npos);
     GX_TRY(call, hipEventRecord(ctx->ev0, st));
@@ -128,8 +129,8 @@ int stats_device(gx_suffix_index* idx, const uint8_t* q, const uint32_t* offs, u
 }
 
 // q: unpadded.  Takes ctx->mu.
-int mems_device(gx_suffix_index* idx, const uint8_t* q, const uint32_t* offs, uint32_t nq, uint32_t L, gx_mem* mems,
-                size_t cap, uint64_t* mem_offsets, uint64_t* candidates) {
+int mems_device(gx_suffix_index* idx, const uint8_t* q, const uint32_t* offs, uint32_t nq, uint32_t strands, uint32_t L,
+                gx_mem* mems, size_t cap, uint64_t* mem_offsets, uint64_t* candidates) {
     gx_context* ctx = idx->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
@@ -144,7 +145,7 @@ int mems_device(gx_suffix_index* idx, const uint8_t* q, const uint32_t* offs, ui
     }
     // counters: [0] seed word steps, [1] candidates, [2] emit word steps
     StagedBatch b;
-    if (const int rc = stage_batch(call, "mems", q, npos, offs, nq, b)) return rc;
+    if (const int rc = stage_batch_strands(call, "mems", q, (size_t)strand_sources(npos, strands), offs, (uint32_t)strand_sources(nq, strands), strands, b)) return rc;
     uint32_t *lo = nullptr, *coff = nullptr, *qid = nullptr, *tmp = nullptr;
     GX_GET(call, lo, npos);
     GX_GET(call, coff, (size_t)npos + 1);
@@ -238,15 +239,16 @@ int mems_device(gx_suffix_index* idx, const uint8_t* q, const uint32_t* offs, ui
 
 // The checks the two entry points share, in their order, then the batch as the drivers take it.  len_name,
 // len: max_len or min_len, refused at 0; mem_offsets: checked when the call has one (want_offsets).
-int match_prologue(const gx_suffix_index* idx, const uint8_t* queries, const uint64_t* offsets, size_t nq,
+int match_prologue(const gx_suffix_index* idx, const uint8_t* queries, const uint64_t* offsets, size_t nq, uint32_t strands,
                    const char* len_name, uint32_t len, bool want_offsets, const uint64_t* mem_offsets, HostBatch& b) {
+    if (const int src = check_strands(strands)) return src;
     if (!idx) return fail(GX_EINVAL, "idx is NULL");
     if (!offsets) return fail(GX_EINVAL, "offsets is NULL");
     if (want_offsets && !mem_offsets) return fail(GX_EINVAL, "mem_offsets is NULL");
     if (len == 0) return fail(GX_EINVAL, std::string(len_name) + " is 0");
-    const int brc = check_batch(kQueries, queries, offsets, nq);
+    const int brc = check_batch(kQueries, queries, offsets, nq, strands);
     if (brc != GX_OK) return brc;
-    narrow_batch(idx, queries, offsets, nq, b);
+    strand_batch(idx, queries, offsets, nq, strands, b);   // (the item batch)
     return GX_OK;
 }
 
@@ -255,25 +257,38 @@ int match_prologue(const gx_suffix_index* idx, const uint8_t* queries, const uin
 // ---------------------------------------------------------------------------
 // C ABI
 
-extern "C" int gx_suffix_index_match_stats(gx_suffix_index* idx, const uint8_t* queries, const uint64_t* offsets, size_t nq,
-                                           uint32_t max_len, gx_match_stat* stats) {
+extern "C" int gx_suffix_index_match_stats_strands(gx_suffix_index* idx, const uint8_t* queries, const uint64_t* offsets,
+                                                   size_t nq, uint32_t strands, uint32_t max_len, gx_match_stat* stats) {
     HostBatch b;
-    const int rc = match_prologue(idx, queries, offsets, nq, "max_len", max_len, false, nullptr, b);
+    const int rc = match_prologue(idx, queries, offsets, nq, strands, "max_len", max_len, false, nullptr, b);
     if (rc != GX_OK) return rc;
     if (offsets[nq] && !stats) return fail(GX_EINVAL, "stats is NULL");
-    if (idx->ctx) return stats_device(idx, queries, b.offs.data(), (uint32_t)nq, max_len, stats);
-    stats_host(idx, b.padded.data(), b.offs.data(), (uint32_t)nq, max_len, stats);
+    const uint32_t items = (uint32_t)(b.offs.size() - 1);
+    if (idx->ctx) return stats_device(idx, queries, b.offs.data(), items, strands, max_len, stats);
+    stats_host(idx, b.padded.data(), b.offs.data(), items, max_len, stats);
     return GX_OK;
+}
+
+extern "C" int gx_suffix_index_match_stats(gx_suffix_index* idx, const uint8_t* queries, const uint64_t* offsets, size_t nq,
+                                           uint32_t max_len, gx_match_stat* stats) {
+    return gx_suffix_index_match_stats_strands(idx, queries, offsets, nq, GX_STRAND_FWD, max_len, stats);
+}
+
+extern "C" int gx_suffix_index_mems_strands(gx_suffix_index* idx, const uint8_t* queries, const uint64_t* offsets, size_t nq,
+                                            uint32_t strands, uint32_t min_len, gx_mem* mems, size_t mems_cap,
+                                            uint64_t* mem_offsets, uint64_t* candidates) {
+    HostBatch b;
+    const int rc = match_prologue(idx, queries, offsets, nq, strands, "min_len", min_len, true, mem_offsets, b);
+    if (rc != GX_OK) return rc;
+    const uint32_t items = (uint32_t)(b.offs.size() - 1);
+    if (idx->ctx) return mems_device(idx, queries, b.offs.data(), items, strands, min_len, mems, mems_cap, mem_offsets, candidates);
+    return mems_host(idx, b.padded.data(), b.offs.data(), items, min_len, mems, mems_cap, mem_offsets, candidates);
 }
 
 extern "C" int gx_suffix_index_mems(gx_suffix_index* idx, const uint8_t* queries, const uint64_t* offsets, size_t nq,
                                     uint32_t min_len, gx_mem* mems, size_t mems_cap, uint64_t* mem_offsets,
                                     uint64_t* candidates) {
-    HostBatch b;
-    const int rc = match_prologue(idx, queries, offsets, nq, "min_len", min_len, true, mem_offsets, b);
-    if (rc != GX_OK) return rc;
-    if (idx->ctx) return mems_device(idx, queries, b.offs.data(), (uint32_t)nq, min_len, mems, mems_cap, mem_offsets, candidates);
-    return mems_host(idx, b.padded.data(), b.offs.data(), (uint32_t)nq, min_len, mems, mems_cap, mem_offsets, candidates);
+    return gx_suffix_index_mems_strands(idx, queries, offsets, nq, GX_STRAND_FWD, min_len, mems, mems_cap, mem_offsets, candidates);
 }
 
 extern "C" int gx_match_info(const gx_context* ctx, uint64_t* candidates, uint64_t* kept, uint64_t* word_compares,

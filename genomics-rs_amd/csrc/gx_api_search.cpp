@@ -29,6 +29,7 @@
 #include "gx_approx.h"
 #include "gx_edit.h"
 #include "gx_search.h"
+#include "gx_strand.h"
 
 // ---------------------------------------------------------------------------
 // shared with gx_api_match.cpp (declared in gx_api.h and gx_api_call.h)
@@ -46,7 +47,7 @@ uint64_t approx_budget() {
 }
 
 // What every call of search mode refuses of a batch before a byte is staged.
-int check_batch(const BatchKind& kind, const uint8_t* bytes, const uint64_t* offsets, size_t n) {
+int check_batch(const BatchKind& kind, const uint8_t* bytes, const uint64_t* offsets, size_t n, uint32_t strands) {
     const std::string noun = kind.noun;
     if (offsets[0] != 0) return fail(GX_EINVAL, "offsets[0] is not 0");
     for (size_t p = 0; p < n; ++p) {
@@ -66,6 +67,15 @@ int check_batch(const BatchKind& kind, const uint8_t* bytes, const uint64_t* off
         if (total + n >= (1ull << 32) || (uint64_t)n + 1 + kSufTile >= (1ull << 32))
             return fail(GX_ERANGE, "search: pattern bytes plus patterns come to " + std::to_string(total + n) +
                                        ", 2^32 or more: split the batch or lower max_hits");
+    }
+    if (strands != GX_STRAND_FWD) {
+        // the same conditions on the item batch's totals, here with the batch's own: before a byte is read
+        const uint64_t items = strand_items(n, strands), itotal = strand_items(total, strands);
+        if (kind.positions ? itotal + kSufTile + kSufPad >= (1ull << 32) || items + 1 + kSufTile >= (1ull << 32)
+                           : itotal + items >= (1ull << 32) || items + 1 + kSufTile >= (1ull << 32))
+            return fail(GX_ERANGE, "strands: " + std::to_string(itotal) + " item bytes in " + std::to_string(items) +
+                                       " items (the batch has " + std::to_string(total) + " bytes in " + std::to_string(n) +
+                                       "), 2^32 or more with what the device adds: split the batch");
     }
     if (total && !bytes) return fail(GX_EINVAL, std::string(kind.plural) + " is NULL");
     // (one flat pass the compiler vectorises; the culprit is looked for only when there is one)
@@ -105,6 +115,62 @@ int stage_batch(DevCall& call, const char* what, const uint8_t* src, size_t tota
     if (!b.pin) return call.done(fail(GX_ENOMEM, std::string(what) + ": pinned staging"));
     b.bytes = bytes;
     b.off = off;
+    call.ctx->strand_items = n;
+    call.ctx->strand_rc_bytes = 0;
+    call.ctx->strand_timed = false;
+    return GX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// both strands: the item batch of a caller's batch, on the host
+// by gx_strand.h's loops and on the device by gx_strand.hip behind the one copy
+
+int check_strands(uint32_t strands) {
+    if (strands < GX_STRAND_FWD || strands > GX_STRAND_BOTH)
+        return fail(GX_EINVAL, "strands is " + std::to_string(strands) + ", not 1 (forward), 2 (reverse) or 3 (both)");
+    return GX_OK;
+}
+
+void strand_batch(const gx_suffix_index* idx, const uint8_t* bytes, const uint64_t* offsets, size_t n, uint32_t strands,
+                  HostBatch& b) {
+    if (strands == GX_STRAND_FWD) return narrow_batch(idx, bytes, offsets, n, b);
+    // (check_batch has held the item batch's totals against the 32-bit conditions)
+    const uint64_t items = strand_items(n, strands), total = strand_items(offsets[n], strands);
+    b.offs.resize(items + 1);
+    strand_item_offsets(offsets, n, strands, b.offs.data());
+    if (idx->ctx) return;
+    b.padded.assign(total + kSufPad, 0);
+    strand_item_bytes(bytes, offsets, n, strands, b.padded.data());
+}
+
+int stage_batch_strands(DevCall& call, const char* what, const uint8_t* src, size_t total_bytes, const uint32_t* offs,
+                        uint32_t n, uint32_t strands, StagedBatch& b) {
+    if (strands == GX_STRAND_FWD) return stage_batch(call, what, src, total_bytes, offs, n, b);
+    gx_context* ctx = call.ctx;
+    const bool both = strands == GX_STRAND_BOTH;
+    const size_t at = both ? total_bytes : 0, items = (size_t)strand_items(n, strands);
+    uint8_t *bytes = nullptr, *fwd = nullptr;
+    uint32_t* off = nullptr;
+    // (the kernel's aligned 8-byte loads may read up to 7 bytes behind the forward bytes)
+    GX_GET(call, bytes, align_up(at + total_bytes + kSufPad, 8));
+    if (both) fwd = bytes;
+    else GX_GET(call, fwd, align_up(total_bytes, 8) + 8);
+    GX_GET(call, off, items + 1);
+    GX_GET(call, b.cnt, 8);
+    if (total_bytes) GX_TRY(call, hipMemcpyAsync(fwd, src, total_bytes, hipMemcpyHostToDevice, call.st));
+    GX_TRY(call, hipMemcpyAsync(off, offs, ((size_t)n + 1) * 4, hipMemcpyHostToDevice, call.st));
+    GX_TRY(call, hipMemsetAsync(b.cnt, 0, 64, call.st));
+    // the reverse items, the padding behind them and, for both strands, the offsets behind off[n]
+    GX_TRY(call, hipEventRecord(ctx->ev_rc0, call.st));
+    GX_TRY(call, launch_strand_rc(fwd, off, n, (uint32_t)total_bytes, bytes, (uint32_t)at, both ? off + n + 1 : nullptr, call.st));
+    GX_TRY(call, hipEventRecord(ctx->ev_rc1, call.st));
+    b.pin = (unsigned long long*)io_pinned(ctx, 128);
+    if (!b.pin) return call.done(fail(GX_ENOMEM, std::string(what) + ": pinned staging"));
+    b.bytes = bytes;
+    b.off = off;
+    ctx->strand_items = items;
+    ctx->strand_rc_bytes = total_bytes;
+    ctx->strand_timed = true;
     return GX_OK;
 }
 
@@ -192,9 +258,9 @@ int search_host(const gx_suffix_index* idx, const uint8_t* pats, const uint32_t*
 }
 
 // pats: the caller's total_bytes pattern bytes, unpadded (the kSufPad zero bytes behind them are set on
-// the device).  Takes ctx->mu.
+// the device); offs, npat: the item batch of those on `strands`.  Takes ctx->mu.
 int search_device(gx_suffix_index* idx, const uint8_t* pats, size_t total_bytes, const uint32_t* offs, uint32_t npat,
-                  gx_search_hit* hits, uint32_t max_hits, uint32_t* positions, size_t cap, uint64_t* hit_offsets) {
+                  uint32_t strands, gx_search_hit* hits, uint32_t max_hits, uint32_t* positions, size_t cap, uint64_t* hit_offsets) {
     gx_context* ctx = idx->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
     HIPCHK(hipSetDevice(ctx->device));
@@ -205,7 +271,7 @@ int search_device(gx_suffix_index* idx, const uint8_t* pats, size_t total_bytes,
     ctx->srch_ms = ctx->srch_locate_ms = 0.0;
     // 1. patterns and offsets, kSufPad zero bytes behind the patterns
     StagedBatch b;
-    if (const int rc = stage_batch(call, "search", pats, total_bytes, offs, npat, b)) return rc;
+    if (const int rc = stage_batch_strands(call, "search", pats, total_bytes, offs, (uint32_t)strand_sources(npat, strands), strands, b)) return rc;
     SrchHit* d_h = nullptr;
     GX_GET(call, d_h, npat);
     // 2. the interval kernel
@@ -423,7 +489,7 @@ int approx_host(const gx_suffix_index* idx, const uint8_t* pats, const uint32_t*
 
 // pats: unpadded, as for search_device.  Takes ctx->mu.
 int approx_device(gx_suffix_index* idx, const uint8_t* pats, size_t total_bytes, const uint32_t* offs, uint32_t npat,
-                  uint32_t k, gx_approx_hit* hits, uint32_t max_hits, uint32_t* positions, uint8_t* distances, size_t cap,
+                  uint32_t strands, uint32_t k, gx_approx_hit* hits, uint32_t max_hits, uint32_t* positions, uint8_t* distances, size_t cap,
                   uint64_t* hit_offsets) {
     gx_context* ctx = idx->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -436,7 +502,7 @@ int approx_device(gx_suffix_index* idx, const uint8_t* pats, size_t total_bytes,
     // patterns and offsets as the exact search stages them; counters: [0] seed word steps, [1] seed hits,
     // [2] verify word steps
     StagedBatch b;
-    if (const int rc = stage_batch(call, "approximate search", pats, total_bytes, offs, npat, b)) return rc;
+    if (const int rc = stage_batch_strands(call, "approximate search", pats, total_bytes, offs, (uint32_t)strand_sources(npat, strands), strands, b)) return rc;
     DevSeeds s;
     if (const int rc = seed_pieces_device(call, idx, b, npat, k1, &ctx->aprx_seed_ms, s)) return rc;
     const uint64_t total = s.total, budget = approx_budget();
@@ -585,7 +651,7 @@ int edit_host(const gx_suffix_index* idx, const uint8_t* pats, const uint32_t* o
 
 // pats: unpadded, as for search_device.  Takes ctx->mu.
 int edit_device(gx_suffix_index* idx, const uint8_t* pats, size_t total_bytes, const uint32_t* offs, uint32_t npat,
-                uint32_t k, gx_edit_hit* hits, uint32_t max_hits, uint32_t* ends, uint8_t* distances, uint32_t* starts,
+                uint32_t strands, uint32_t k, gx_edit_hit* hits, uint32_t max_hits, uint32_t* ends, uint8_t* distances, uint32_t* starts,
                 size_t cap, uint64_t* hit_offsets) {
     gx_context* ctx = idx->ctx;
     std::lock_guard<std::mutex> lk(ctx->mu);
@@ -597,7 +663,7 @@ int edit_device(gx_suffix_index* idx, const uint8_t* pats, size_t total_bytes, c
     ctx->edit_seed_ms = ctx->edit_verify_ms = ctx->edit_dedupe_ms = 0.0;
     // counters: [0] seed word steps, [1] seed hits, [2] ends before dedupe, [3] cell updates
     StagedBatch b;
-    if (const int rc = stage_batch(call, "edit search", pats, total_bytes, offs, npat, b)) return rc;
+    if (const int rc = stage_batch_strands(call, "edit search", pats, total_bytes, offs, (uint32_t)strand_sources(npat, strands), strands, b)) return rc;
     // pieces, seeds, their 64-bit total, candidate offsets: DESIGN.md 19.2 stages 1 to 4
     DevSeeds s;
     if (const int rc = seed_pieces_device(call, idx, b, npat, k1, &ctx->edit_seed_ms, s)) return rc;
@@ -792,12 +858,13 @@ constexpr SearchKind kExact{nullptr, "positions", nullptr, 0};
 constexpr SearchKind kApprox{"approximate search", "positions", "window", 0};
 constexpr SearchKind kEdit{"edit search", "ends", "end", kEditMaxM};
 
-// The checks of an entry point in their order, then the batch as the drivers take it.  *run: there is a
-// pattern to search for (without one hit_offsets[0] = 0 is the whole answer).
+// The checks of an entry point in their order, then the item batch of the caller's batch on `strands` as the
+// drivers take it.  *run: there is a pattern to search for (without one hit_offsets[0] = 0 is the whole answer).
 int search_prologue(const SearchKind& kind, const gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets,
-                    size_t npat, uint32_t k, const void* hits, const void* out, const void* distances, const void* starts,
+                    size_t npat, uint32_t strands, uint32_t k, const void* hits, const void* out, const void* distances, const void* starts,
                     uint64_t* hit_offsets, HostBatch& b, bool* run) {
     *run = false;
+    if (const int src = check_strands(strands)) return src;
     if (!idx) return fail(GX_EINVAL, "idx is NULL");
     if (!offsets) return fail(GX_EINVAL, "offsets is NULL");
     if (npat && !hits) return fail(GX_EINVAL, "hits is NULL");
@@ -807,7 +874,7 @@ int search_prologue(const SearchKind& kind, const gx_suffix_index* idx, const ui
         if (starts && !out) return fail(GX_EINVAL, "starts without ends");
         if (k > kAprxMaxK) return fail(GX_EINVAL, "k is " + std::to_string(k) + ", more than GX_APPROX_MAX_K = 8");
     }
-    const int brc = check_batch(kPatterns, patterns, offsets, npat);
+    const int brc = check_batch(kPatterns, patterns, offsets, npat, strands);
     if (brc != GX_OK) return brc;
     if (kind.what) {
         for (size_t p = 0; p < npat; ++p) {
@@ -830,24 +897,39 @@ int search_prologue(const SearchKind& kind, const gx_suffix_index* idx, const ui
         if (hit_offsets) hit_offsets[0] = 0;
         return GX_OK;
     }
-    narrow_batch(idx, patterns, offsets, npat, b);
+    // (the caller's batch has passed: now its item batch)
+    strand_batch(idx, patterns, offsets, npat, strands, b);
+    if (kind.what) {
+        const uint64_t npieces = (uint64_t)(b.offs.size() - 1) * (k + 1);   // (as above, of the items)
+        if (npieces + 1 + kSufTile >= (1ull << 32))
+            return fail(GX_ERANGE, std::string(kind.what) + ": " + std::to_string(npieces) +
+                                       " pieces (npat * (k + 1)), 2^32 or more with the scan's rounding: split the batch");
+    }
     *run = true;
     return GX_OK;
 }
 
 }  // namespace
 
+extern "C" int gx_suffix_index_search_strands(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets,
+                                              size_t npat, uint32_t strands, gx_search_hit* hits, uint32_t max_hits,
+                                              uint32_t* positions, size_t positions_cap, uint64_t* hit_offsets) {
+    HostBatch b;
+    bool run;
+    const int rc = search_prologue(kExact, idx, patterns, offsets, npat, strands, 0, hits, positions, nullptr, nullptr, hit_offsets, b, &run);
+    if (!run) return rc;
+    const size_t items = b.offs.size() - 1;
+    if (idx->ctx)
+        return search_device(idx, patterns, (size_t)offsets[npat], b.offs.data(), (uint32_t)items, strands, hits, max_hits,
+                             positions, positions_cap, hit_offsets);
+    return search_host(idx, b.padded.data(), b.offs.data(), items, hits, max_hits, positions, positions_cap, hit_offsets);
+}
+
 extern "C" int gx_suffix_index_search(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets, size_t npat,
                                       gx_search_hit* hits, uint32_t max_hits, uint32_t* positions, size_t positions_cap,
                                       uint64_t* hit_offsets) {
-    HostBatch b;
-    bool run;
-    const int rc = search_prologue(kExact, idx, patterns, offsets, npat, 0, hits, positions, nullptr, nullptr, hit_offsets, b, &run);
-    if (!run) return rc;
-    if (idx->ctx)
-        return search_device(idx, patterns, (size_t)offsets[npat], b.offs.data(), (uint32_t)npat, hits, max_hits, positions,
-                             positions_cap, hit_offsets);
-    return search_host(idx, b.padded.data(), b.offs.data(), npat, hits, max_hits, positions, positions_cap, hit_offsets);
+    return gx_suffix_index_search_strands(idx, patterns, offsets, npat, GX_STRAND_FWD, hits, max_hits, positions, positions_cap,
+                                          hit_offsets);
 }
 
 extern "C" int gx_search_info(const gx_context* ctx, uint64_t* word_compares, double* search_ms, double* locate_ms) {
@@ -858,19 +940,28 @@ extern "C" int gx_search_info(const gx_context* ctx, uint64_t* word_compares, do
     return GX_OK;
 }
 
+extern "C" int gx_suffix_index_search_approx_strands(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets,
+                                                     size_t npat, uint32_t strands, uint32_t k, gx_approx_hit* hits,
+                                                     uint32_t max_hits, uint32_t* positions, uint8_t* distances,
+                                                     size_t positions_cap, uint64_t* hit_offsets) {
+    HostBatch b;
+    bool run;
+    const int rc = search_prologue(kApprox, idx, patterns, offsets, npat, strands, k, hits, positions, distances, nullptr, hit_offsets, b, &run);
+    if (!run) return rc;
+    const size_t items = b.offs.size() - 1;
+    if (idx->ctx)
+        return approx_device(idx, patterns, (size_t)offsets[npat], b.offs.data(), (uint32_t)items, strands, k, hits, max_hits,
+                             positions, distances, positions_cap, hit_offsets);
+    return approx_host(idx, b.padded.data(), b.offs.data(), items, k, hits, max_hits, positions, distances, positions_cap,
+                       hit_offsets);
+}
+
 extern "C" int gx_suffix_index_search_approx(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets,
                                              size_t npat, uint32_t k, gx_approx_hit* hits, uint32_t max_hits,
                                              uint32_t* positions, uint8_t* distances, size_t positions_cap,
                                              uint64_t* hit_offsets) {
-    HostBatch b;
-    bool run;
-    const int rc = search_prologue(kApprox, idx, patterns, offsets, npat, k, hits, positions, distances, nullptr, hit_offsets, b, &run);
-    if (!run) return rc;
-    if (idx->ctx)
-        return approx_device(idx, patterns, (size_t)offsets[npat], b.offs.data(), (uint32_t)npat, k, hits, max_hits, positions,
-                             distances, positions_cap, hit_offsets);
-    return approx_host(idx, b.padded.data(), b.offs.data(), npat, k, hits, max_hits, positions, distances, positions_cap,
-                       hit_offsets);
+    return gx_suffix_index_search_approx_strands(idx, patterns, offsets, npat, GX_STRAND_FWD, k, hits, max_hits, positions,
+                                                 distances, positions_cap, hit_offsets);
 }
 
 extern "C" int gx_approx_info(const gx_context* ctx, uint64_t* candidates, uint64_t* word_compares, double* seed_ms,
@@ -883,19 +974,28 @@ extern "C" int gx_approx_info(const gx_context* ctx, uint64_t* candidates, uint6
     return GX_OK;
 }
 
+extern "C" int gx_suffix_index_search_edit_strands(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets,
+                                                   size_t npat, uint32_t strands, uint32_t k, gx_edit_hit* hits,
+                                                   uint32_t max_hits, uint32_t* ends, uint8_t* distances, uint32_t* starts,
+                                                   size_t positions_cap, uint64_t* hit_offsets) {
+    HostBatch b;
+    bool run;
+    const int rc = search_prologue(kEdit, idx, patterns, offsets, npat, strands, k, hits, ends, distances, starts, hit_offsets, b, &run);
+    if (!run) return rc;
+    const size_t items = b.offs.size() - 1;
+    if (idx->ctx)
+        return edit_device(idx, patterns, (size_t)offsets[npat], b.offs.data(), (uint32_t)items, strands, k, hits, max_hits, ends,
+                           distances, starts, positions_cap, hit_offsets);
+    return edit_host(idx, b.padded.data(), b.offs.data(), items, k, hits, max_hits, ends, distances, starts, positions_cap,
+                     hit_offsets);
+}
+
 extern "C" int gx_suffix_index_search_edit(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets,
                                            size_t npat, uint32_t k, gx_edit_hit* hits, uint32_t max_hits, uint32_t* ends,
                                            uint8_t* distances, uint32_t* starts, size_t positions_cap,
                                            uint64_t* hit_offsets) {
-    HostBatch b;
-    bool run;
-    const int rc = search_prologue(kEdit, idx, patterns, offsets, npat, k, hits, ends, distances, starts, hit_offsets, b, &run);
-    if (!run) return rc;
-    if (idx->ctx)
-        return edit_device(idx, patterns, (size_t)offsets[npat], b.offs.data(), (uint32_t)npat, k, hits, max_hits, ends,
-                           distances, starts, positions_cap, hit_offsets);
-    return edit_host(idx, b.padded.data(), b.offs.data(), npat, k, hits, max_hits, ends, distances, starts, positions_cap,
-                     hit_offsets);
+    return gx_suffix_index_search_edit_strands(idx, patterns, offsets, npat, GX_STRAND_FWD, k, hits, max_hits, ends, distances,
+                                               starts, positions_cap, hit_offsets);
 }
 
 extern "C" int gx_edit_info(const gx_context* ctx, uint64_t* candidates, uint64_t* pre_dedupe_ends, uint64_t* cell_updates,
@@ -907,5 +1007,66 @@ extern "C" int gx_edit_info(const gx_context* ctx, uint64_t* candidates, uint64_
     if (seed_ms) *seed_ms = ctx->edit_seed_ms;
     if (verify_ms) *verify_ms = ctx->edit_verify_ms;
     if (dedupe_ms) *dedupe_ms = ctx->edit_dedupe_ms;
+    return GX_OK;
+}
+
+// ---------------------------------------------------------------------------
+// both strands: the reverse complement as a call of its own
+
+namespace {
+constexpr BatchKind kItems{"pattern", "bytes", 0, true};
+}
+
+extern "C" int gx_revcomp(const uint8_t* src, size_t n, uint8_t* dst) {
+    if (n && (!src || !dst)) return fail(GX_EINVAL, "NULL argument");
+    if (n) strand_rc(src, n, dst);
+    return GX_OK;
+}
+
+extern "C" int gx_revcomp_batch(gx_context* ctx, const uint8_t* bytes, const uint64_t* offsets, size_t n, uint32_t strands,
+                                uint8_t* out_bytes, size_t out_cap, uint64_t* out_offsets) {
+    if (const int src = check_strands(strands)) return src;
+    if (!offsets) return fail(GX_EINVAL, "offsets is NULL");
+    if (!out_offsets) return fail(GX_EINVAL, "out_offsets is NULL");
+    const int brc = check_batch(kItems, bytes, offsets, n, strands);
+    if (brc != GX_OK) return brc;
+    gx_suffix_index where;   // (only its ctx is read: which side builds the bytes)
+    where.ctx = ctx;
+    HostBatch b;
+    strand_batch(&where, bytes, offsets, n, strands, b);
+    const size_t items = b.offs.size() - 1, total = b.offs[items];
+    for (size_t p = 0; p <= items; ++p) out_offsets[p] = b.offs[p];
+    if (!out_bytes) return GX_OK;
+    if (total > out_cap)
+        return fail(GX_ECAP, "revcomp: " + std::to_string(total) + " item bytes needed, out_cap is " + std::to_string(out_cap));
+    // (with room for them the kSufPad zero bytes behind the items are handed out too, as staged)
+    const size_t want = out_cap - total >= (size_t)kSufPad ? total + kSufPad : total;
+    if (!ctx) {
+        if (want) memcpy(out_bytes, b.padded.data(), want);
+        return GX_OK;
+    }
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    HIPCHK(hipSetDevice(ctx->device));
+    DevCall call(ctx);
+    StagedBatch sb;
+    if (const int rc = stage_batch_strands(call, "revcomp", bytes, (size_t)offsets[n], b.offs.data(), (uint32_t)n, strands, sb))
+        return rc;
+    // the offsets as the device holds them
+    GX_TRY(call, hipMemcpyAsync(b.offs.data(), sb.off, (items + 1) * 4, hipMemcpyDeviceToHost, call.st));
+    if (want) GX_TRY(call, hipMemcpyAsync(out_bytes, sb.bytes, want, hipMemcpyDeviceToHost, call.st));
+    GX_TRY(call, hipStreamSynchronize(call.st));
+    for (size_t p = 0; p <= items; ++p) out_offsets[p] = b.offs[p];
+    return call.done(GX_OK);   // (the stream is idle)
+}
+
+extern "C" int gx_strand_info(const gx_context* ctx, uint64_t* items, uint64_t* rc_bytes, double* rc_ms) {
+    if (!ctx) return fail(GX_EINVAL, "ctx is NULL");
+    if (items) *items = ctx->strand_items;
+    if (rc_bytes) *rc_bytes = ctx->strand_rc_bytes;
+    if (rc_ms) {
+        // (every call leaves its stream idle: the two events have completed)
+        float ms = 0.f;
+        *rc_ms = ctx->strand_timed && hipEventElapsedTime(&ms, ctx->ev_rc0, ctx->ev_rc1) == hipSuccess ? ms : 0.0;
+    }
     return GX_OK;
 }

@@ -69,6 +69,15 @@
 //       query name, chain number within the query, score, n_anchors, qstart,
 //       qend, tstart, tend; after them one line per query without a chain:
 //       name, -, 0.
+//   gx-align search ... --strands forward|reverse|both
+//       In every sub-mode above: the records are searched on the chosen strands
+//       (the _strands calls).  A line per item: with "both" every
+//       record on the forward strand first, then every record's reverse
+//       complement.  Every line gains a strand column, + or -, directly behind
+//       the name; with --mem and --chain the record's length follows it, since a
+//       - line's qpos counts in the reverse complement (the same bases begin at
+//       length - qpos - len in the record).  Text positions are the forward
+//       genome's.  Without the flag the output is what it always was.
 #include <algorithm>
 #include <chrono>
 #include <cstdio>
@@ -94,9 +103,9 @@ void usage() {
             "       gx-align compare -d|--fasta-dir <DIR> [-o <TSV>]\n"
             "       gx-align suffix-tree -f|--fasta-path <FASTA> [-a|--alphabet-file <ALPHABET>] [--suffix-links] "
             "[--stats] [-o <BWT>]\n"
-            "       gx-align search -f|--fasta-path <GENOME> -p|--patterns <PATTERNS> [--max-hits <K>] [-k <MISMATCHES> | -e <EDITS> [--cigar]] [-o <TSV>]\n"
+            "       gx-align search -f|--fasta-path <GENOME> -p|--patterns <PATTERNS> [--max-hits <K>] [-k <MISMATCHES> | -e <EDITS> [--cigar]] [--strands forward|reverse|both] [-o <TSV>]\n"
             "       gx-align search -f|--fasta-path <GENOME> -p|--patterns <QUERIES> --mem <MIN_LEN> [--chain [--chain-gap <G>] "
-            "[--chain-drift <D>] [--chain-pred <H>] [--chain-min-score <S>]] [-o <TSV>]\n");
+            "[--chain-drift <D>] [--chain-pred <H>] [--chain-min-score <S>]] [--strands forward|reverse|both] [-o <TSV>]\n");
 }
 
 struct Records {
@@ -478,8 +487,10 @@ int run_suffix_tree(const std::string& fasta, const std::string& alphabet, bool 
 // -k K: at most K substitutions (gx_suffix_index_search_approx); -e K: at most K
 // differences (gx_suffix_index_search_edit); both below 0: exact.  sc (with -e alone): the
 // reported windows are aligned under these scores on the band of K (gx_suffix_index_extend).
+// strands: 0 without --strands (the forward strand, lines as they always were), else GX_STRAND_*: a line per item of
+// the item batch, '+' or '-' behind the name.
 int run_search(const std::string& fasta, const std::string& patterns, uint32_t max_hits, const std::string& out_path,
-               int kmis, int kedit, const gx_scores* sc) {
+               int kmis, int kedit, const gx_scores* sc, uint32_t strands) {
     const char* lg = getenv("GX_LOG");
     const bool info = lg && (!strcmp(lg, "info") || !strcmp(lg, "debug"));
     if (info) fprintf(stderr, "[INFO] MODE: Search\n[INFO] Loading sequences from %s and %s\n", fasta.c_str(), patterns.c_str());
@@ -487,10 +498,12 @@ int run_search(const std::string& fasta, const std::string& patterns, uint32_t m
     load_fasta(fasta, g);
     load_fasta(patterns, q);
     if (!g.size()) { fprintf(stderr, "[ERROR] no record in %s\n", fasta.c_str()); return 1; }
-    const size_t npat = q.size();
+    const size_t ncall = q.size();
+    const uint32_t st = strands ? strands : GX_STRAND_FWD;
+    const size_t npat = ncall * (st == GX_STRAND_BOTH ? 2 : 1);   // the items
     std::vector<uint8_t> packed;
-    std::vector<uint64_t> off(npat + 1, 0);
-    for (size_t p = 0; p < npat; ++p) {
+    std::vector<uint64_t> off(ncall + 1, 0);
+    for (size_t p = 0; p < ncall; ++p) {
         packed.insert(packed.end(), q.seq(p), q.seq(p) + q.sl[p]);
         off[p + 1] = packed.size();
     }
@@ -512,16 +525,18 @@ int run_search(const std::string& fasta, const std::string& patterns, uint32_t m
     t0 = std::chrono::steady_clock::now();
     for (int pass = 0; pass < 2; ++pass) {   // GX_ECAP: hit_offsets is complete; allocate and repeat
         if (exact)
-            rc = gx_suffix_index_search(idx, packed.data(), off.data(), npat, hits.data(), max_hits,
-                                        max_hits ? pos.data() : nullptr, pos.size(), max_hits ? hoff.data() : nullptr);
+            rc = gx_suffix_index_search_strands(idx, packed.data(), off.data(), ncall, st, hits.data(), max_hits,
+                                                max_hits ? pos.data() : nullptr, pos.size(), max_hits ? hoff.data() : nullptr);
         else if (kedit >= 0)
-            rc = gx_suffix_index_search_edit(idx, packed.data(), off.data(), npat, (uint32_t)kedit, ehits.data(), max_hits,
-                                             max_hits ? pos.data() : nullptr, max_hits ? dst.data() : nullptr,
-                                             max_hits ? sta.data() : nullptr, pos.size(), max_hits ? hoff.data() : nullptr);
+            rc = gx_suffix_index_search_edit_strands(idx, packed.data(), off.data(), ncall, st, (uint32_t)kedit, ehits.data(),
+                                                     max_hits, max_hits ? pos.data() : nullptr, max_hits ? dst.data() : nullptr,
+                                                     max_hits ? sta.data() : nullptr, pos.size(),
+                                                     max_hits ? hoff.data() : nullptr);
         else
-            rc = gx_suffix_index_search_approx(idx, packed.data(), off.data(), npat, (uint32_t)kmis, ahits.data(), max_hits,
-                                               max_hits ? pos.data() : nullptr, max_hits ? dst.data() : nullptr, pos.size(),
-                                               max_hits ? hoff.data() : nullptr);
+            rc = gx_suffix_index_search_approx_strands(idx, packed.data(), off.data(), ncall, st, (uint32_t)kmis, ahits.data(),
+                                                       max_hits, max_hits ? pos.data() : nullptr,
+                                                       max_hits ? dst.data() : nullptr, pos.size(),
+                                                       max_hits ? hoff.data() : nullptr);
         if (rc != GX_ECAP) break;
         pos.assign((size_t)hoff[npat], 0);
         if (!exact) dst.assign((size_t)hoff[npat], 0);
@@ -535,12 +550,12 @@ int run_search(const std::string& fasta, const std::string& patterns, uint32_t m
         t0 = std::chrono::steady_clock::now();
         xhits.resize((size_t)hoff[npat] + 1);
         coff.assign((size_t)hoff[npat] + 1, 0);
-        rc = gx_suffix_index_extend(idx, packed.data(), off.data(), npat, hoff.data(), sta.data(), pos.data(), sc,
-                                    (uint32_t)kedit, xhits.data(), nullptr, 0, coff.data());
+        rc = gx_suffix_index_extend_strands(idx, packed.data(), off.data(), ncall, st, hoff.data(), sta.data(), pos.data(), sc,
+                                            (uint32_t)kedit, xhits.data(), nullptr, 0, coff.data());
         if (rc == GX_OK) {
             cig.resize((size_t)coff.back() + 1);
-            rc = gx_suffix_index_extend(idx, packed.data(), off.data(), npat, hoff.data(), sta.data(), pos.data(), sc,
-                                        (uint32_t)kedit, xhits.data(), cig.data(), cig.size(), coff.data());
+            rc = gx_suffix_index_extend_strands(idx, packed.data(), off.data(), ncall, st, hoff.data(), sta.data(), pos.data(),
+                                                sc, (uint32_t)kedit, xhits.data(), cig.data(), cig.size(), coff.data());
         }
         const auto xus = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
         if (rc == GX_OK && info) {
@@ -584,8 +599,11 @@ int run_search(const std::string& fasta, const std::string& patterns, uint32_t m
     FILE* f = out_path.empty() ? stdout : fopen(out_path.c_str(), "w");
     if (!f) { fprintf(stderr, "[ERROR] cannot write %s\n", out_path.c_str()); return 1; }
     for (size_t p = 0; p < npat; ++p) {
+        // (item p is record p % ncall, on the - strand in the reverse items; the strand column only with --strands)
+        const size_t c = p % ncall;
+        const std::string name = q.name(c) + (strands ? (st == GX_STRAND_REV || p >= ncall ? "\t-" : "\t+") : "");
         if (kedit >= 0) {   // name, length, count, best_dist, best_end, start-end:dist triples
-            fprintf(f, "%s\t%llu\t%u\t%u\t%u\t", q.name(p).c_str(), (unsigned long long)q.sl[p], ehits[p].count,
+            fprintf(f, "%s\t%llu\t%u\t%u\t%u\t", name.c_str(), (unsigned long long)q.sl[c], ehits[p].count,
                     ehits[p].best_dist, ehits[p].best_end);
             for (uint64_t k = hoff[p]; k < hoff[p + 1]; ++k) {
                 fprintf(f, k == hoff[p] ? "%u-%u:%u" : ",%u-%u:%u", sta[k], pos[k], (unsigned)dst[k]);
@@ -594,11 +612,11 @@ int run_search(const std::string& fasta, const std::string& patterns, uint32_t m
                 for (uint64_t r = coff[k]; r < coff[k + 1]; ++r) fprintf(f, "%u%c", cig[r] >> 4, "MID?"[cig[r] & 3u]);
             }
         } else if (exact) {
-            fprintf(f, "%s\t%llu\t%u\t%u\t%u\t", q.name(p).c_str(), (unsigned long long)q.sl[p], hits[p].count,
+            fprintf(f, "%s\t%llu\t%u\t%u\t%u\t", name.c_str(), (unsigned long long)q.sl[c], hits[p].count,
                     hits[p].prefix_len, hits[p].prefix_pos);
             for (uint64_t k = hoff[p]; k < hoff[p + 1]; ++k) fprintf(f, k == hoff[p] ? "%u" : ",%u", pos[k]);
         } else {   // name, length, count, best_dist, best_pos, pos:dist pairs
-            fprintf(f, "%s\t%llu\t%u\t%u\t%u\t", q.name(p).c_str(), (unsigned long long)q.sl[p], ahits[p].count,
+            fprintf(f, "%s\t%llu\t%u\t%u\t%u\t", name.c_str(), (unsigned long long)q.sl[c], ahits[p].count,
                     ahits[p].best_dist, ahits[p].best_pos);
             for (uint64_t k = hoff[p]; k < hoff[p + 1]; ++k)
                 fprintf(f, k == hoff[p] ? "%u:%u" : ",%u:%u", pos[k], (unsigned)dst[k]);
@@ -611,8 +629,10 @@ int run_search(const std::string& fasta, const std::string& patterns, uint32_t m
 
 // search --mem L on GPU 0: the MEMs of every record of the query file against the genome's first record.
 // chain: with --chain, the parameters of gx_chain_anchors on those MEMs; the file then holds the chains.
+// strands: as for run_search; with --strands the query length follows the strand column, so that a reader can map
+// a - item's qpos back: the same bases begin at length - qpos - len in the record.
 int run_mems(const std::string& fasta, const std::string& queries, uint32_t min_len, const std::string& out_path,
-             const gx_chain_params* chain) {
+             const gx_chain_params* chain, uint32_t strands) {
     const char* lg = getenv("GX_LOG");
     const bool info = lg && (!strcmp(lg, "info") || !strcmp(lg, "debug"));
     if (info) fprintf(stderr, "[INFO] MODE: Search (MEMs)\n[INFO] Loading sequences from %s and %s\n", fasta.c_str(), queries.c_str());
@@ -620,10 +640,12 @@ int run_mems(const std::string& fasta, const std::string& queries, uint32_t min_
     load_fasta(fasta, g);
     load_fasta(queries, q);
     if (!g.size()) { fprintf(stderr, "[ERROR] no record in %s\n", fasta.c_str()); return 1; }
-    const size_t nq = q.size();
+    const size_t ncall = q.size();
+    const uint32_t st = strands ? strands : GX_STRAND_FWD;
+    const size_t nq = ncall * (st == GX_STRAND_BOTH ? 2 : 1);   // the items
     std::vector<uint8_t> packed;
-    std::vector<uint64_t> off(nq + 1, 0), moff(nq + 1, 0), cand(nq + 1, 0);
-    for (size_t c = 0; c < nq; ++c) {
+    std::vector<uint64_t> off(ncall + 1, 0), moff(nq + 1, 0), cand(nq + 1, 0);
+    for (size_t c = 0; c < ncall; ++c) {
         packed.insert(packed.end(), q.seq(c), q.seq(c) + q.sl[c]);
         off[c + 1] = packed.size();
     }
@@ -637,10 +659,11 @@ int run_mems(const std::string& fasta, const std::string& queries, uint32_t min_
     std::vector<gx_mem> mems;
     t0 = std::chrono::steady_clock::now();
     // the counts first, then the exact capacity
-    rc = gx_suffix_index_mems(idx, packed.data(), off.data(), nq, min_len, nullptr, 0, moff.data(), cand.data());
+    rc = gx_suffix_index_mems_strands(idx, packed.data(), off.data(), ncall, st, min_len, nullptr, 0, moff.data(), cand.data());
     if (rc == GX_OK && moff[nq]) {
         mems.resize((size_t)moff[nq]);
-        rc = gx_suffix_index_mems(idx, packed.data(), off.data(), nq, min_len, mems.data(), mems.size(), moff.data(), cand.data());
+        rc = gx_suffix_index_mems_strands(idx, packed.data(), off.data(), ncall, st, min_len, mems.data(), mems.size(), moff.data(),
+                                          cand.data());
     }
     const auto us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
     if (rc == GX_OK && info) {
@@ -649,7 +672,7 @@ int run_mems(const std::string& fasta, const std::string& queries, uint32_t min_
         gx_match_info(ctx, &cands, &kept, &words, &tms, &sms, &ems);
         fprintf(stderr, "[INFO] index of %llu bases built in %lld us; %zu queries of %llu bases matched at min_len %u in %lld us "
                         "(%llu candidates, %llu MEMs, %llu word compares, seeds %.3f ms, emit %.3f ms)\n",
-                (unsigned long long)g.sl[0], (long long)build_us, nq, (unsigned long long)off[nq], min_len, (long long)us,
+                (unsigned long long)g.sl[0], (long long)build_us, nq, (unsigned long long)(off[ncall] * (nq / std::max<size_t>(ncall, 1))), min_len, (long long)us,
                 (unsigned long long)cands, (unsigned long long)kept, (unsigned long long)words, sms, ems);
     }
     gx_suffix_index_free(idx);
@@ -686,21 +709,27 @@ int run_mems(const std::string& fasta, const std::string& queries, uint32_t min_
     if (rc != GX_OK) return fail_msg(mems_rc != GX_OK ? "search --mem" : "search --chain", rc);
     FILE* f = out_path.empty() ? stdout : fopen(out_path.c_str(), "w");
     if (!f) { fprintf(stderr, "[ERROR] cannot write %s\n", out_path.c_str()); return 1; }
+    // an item's name: its record's, and with --strands the strand and the record's length behind it
+    auto name_of = [&](size_t c) {
+        std::string s = q.name(c % ncall);
+        if (strands) s += (st == GX_STRAND_REV || c >= ncall ? "\t-\t" : "\t+\t") + std::to_string(q.sl[c % ncall]);
+        return s;
+    };
     if (chain) {
         for (size_t c = 0; c < nq; ++c)
             for (uint64_t k = coff[c]; k < coff[c + 1]; ++k)
-                fprintf(f, "%s\t%llu\t%d\t%u\t%u\t%u\t%u\t%u\n", q.name(c).c_str(), (unsigned long long)(k - coff[c]),
+                fprintf(f, "%s\t%llu\t%d\t%u\t%u\t%u\t%u\t%u\n", name_of(c).c_str(), (unsigned long long)(k - coff[c]),
                         chains[k].score, chains[k].n_anchors, chains[k].qstart, chains[k].qend, chains[k].tstart, chains[k].tend);
         for (size_t c = 0; c < nq; ++c)
-            if (coff[c + 1] == coff[c]) fprintf(f, "%s\t-\t0\n", q.name(c).c_str());
+            if (coff[c + 1] == coff[c]) fprintf(f, "%s\t-\t0\n", name_of(c).c_str());
         if (f != stdout) fclose(f);
         return 0;
     }
     for (size_t c = 0; c < nq; ++c)
         for (uint64_t k = moff[c]; k < moff[c + 1]; ++k)
-            fprintf(f, "%s\t%u\t%u\t%u\n", q.name(c).c_str(), mems[k].qpos, mems[k].tpos, mems[k].len);
+            fprintf(f, "%s\t%u\t%u\t%u\n", name_of(c).c_str(), mems[k].qpos, mems[k].tpos, mems[k].len);
     for (size_t c = 0; c < nq; ++c)
-        if (moff[c + 1] == moff[c]) fprintf(f, "%s\t-\t-\t0\n", q.name(c).c_str());
+        if (moff[c + 1] == moff[c]) fprintf(f, "%s\t-\t-\t0\n", name_of(c).c_str());
     if (f != stdout) fclose(f);
     return 0;
 }
@@ -712,6 +741,7 @@ int main(int argc, char** argv) {
     setenv("GX_LOG", getenv("GX_LOG") ? getenv("GX_LOG") : "info", 1);
     std::string config = "config.toml", type, fasta, dir, tsv = "similarity_matrix.tsv", mode, patterns;
     int ngpu = 0;
+    uint32_t strands = 0;   // (0: no --strands)
     long long max_hits = 16, kmis = -1, kedit = -1, mem_len = -1;
     bool with_self = true, stats = false, out_set = false, cigar = false, chain = false, chain_opt = false;
     gx_chain_params cp{GX_CHAIN_DEFAULT_W_MATCH,  GX_CHAIN_DEFAULT_W_DRIFT,  GX_CHAIN_DEFAULT_MAX_GAP,
@@ -743,6 +773,12 @@ int main(int argc, char** argv) {
         else if (a == "--cigar") cigar = true;
         else if (a == "--mem") { std::string v; next(v); mem_len = atoll(v.c_str()); if (mem_len < 1 || mem_len > 0xFFFFFFFFll) { usage(); return 2; } }
         else if (a == "--chain") chain = true;
+        else if (a == "--strands") {
+            std::string v;
+            next(v);
+            strands = v == "forward" ? GX_STRAND_FWD : v == "reverse" ? GX_STRAND_REV : v == "both" ? GX_STRAND_BOTH : 0;
+            if (!strands) { usage(); return 2; }
+        }
         else if (a == "--chain-gap" || a == "--chain-drift" || a == "--chain-pred" || a == "--chain-min-score") {
             std::string v;
             long long x = 0;
@@ -763,21 +799,22 @@ int main(int argc, char** argv) {
     if (mode.empty() || (by_file && fasta.empty()) || (!by_file && dir.empty()) ||
         (mode == "search" && (patterns.empty() || max_hits < 0 || max_hits > 0xFFFFFFFFll || kmis > 0xFFFF || kedit > 0xFFFF ||
                               (kmis >= 0 && kedit >= 0) || (mem_len >= 0 && (kmis >= 0 || kedit >= 0)))) ||
-        (cigar && (mode != "search" || kedit < 0)) || (chain && (mode != "search" || mem_len < 0)) || (chain_opt && !chain)) {
+        (cigar && (mode != "search" || kedit < 0)) || (chain && (mode != "search" || mem_len < 0)) || (chain_opt && !chain) ||
+        (strands && mode != "search")) {
         usage();
         return 2;
     }
     if (mode == "compare") return run_compare(dir, tsv);   // (reads no scores: main.rs:216-221)
-    if (mode == "search" && mem_len >= 0) return run_mems(fasta, patterns, (uint32_t)mem_len, out_set ? tsv : std::string(), chain ? &cp : nullptr);
+    if (mode == "search" && mem_len >= 0) return run_mems(fasta, patterns, (uint32_t)mem_len, out_set ? tsv : std::string(), chain ? &cp : nullptr, strands);
     if (mode == "search" && !cigar)
-        return run_search(fasta, patterns, (uint32_t)max_hits, out_set ? tsv : std::string(), (int)kmis, (int)kedit, nullptr);
+        return run_search(fasta, patterns, (uint32_t)max_hits, out_set ? tsv : std::string(), (int)kmis, (int)kedit, nullptr, strands);
     if (mode == "suffix-tree") return run_suffix_tree(fasta, type, stats, out_set ? tsv : std::string());
     gx_scores sc;
     if (gx_config_load(config.c_str(), &sc) != GX_OK) {
         fprintf(stderr, "[ERROR] %s\n", gx_last_error());
         return 1;  // config.rs: exit(1)
     }
-    if (mode == "search") return run_search(fasta, patterns, (uint32_t)max_hits, out_set ? tsv : std::string(), -1, (int)kedit, &sc);
+    if (mode == "search") return run_search(fasta, patterns, (uint32_t)max_hits, out_set ? tsv : std::string(), -1, (int)kedit, &sc, strands);
     if (mode == "align") return run_align(sc, type.empty() ? "local" : type, fasta);  // main.rs:35 default "local"
     return run_all_vs_all(sc, type.empty() ? "global" : type, dir, tsv, ngpu, with_self);
 }

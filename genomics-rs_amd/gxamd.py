@@ -101,7 +101,11 @@ EXPORTED = ["gx_last_error", "gx_version", "gx_context_create", "gx_context_dest
             "gx_suffix_index_search_edit", "gx_edit_info",
             "gx_suffix_index_match_stats", "gx_suffix_index_mems", "gx_match_info",
             "gx_suffix_index_extend", "gx_extend_info",
-            "gx_chain_anchors", "gx_chain_info"]
+            "gx_chain_anchors", "gx_chain_info",
+            "gx_revcomp", "gx_revcomp_batch", "gx_strand_info",
+            "gx_suffix_index_search_strands", "gx_suffix_index_search_approx_strands",
+            "gx_suffix_index_search_edit_strands", "gx_suffix_index_extend_strands",
+            "gx_suffix_index_match_stats_strands", "gx_suffix_index_mems_strands"]
 
 _lib = None
 
@@ -211,6 +215,17 @@ def lib():
     L.gx_extend_info.argtypes = [vp, u64p, u64p, u64p, u64p, dp, dp]
     L.gx_chain_anchors.argtypes = [vp, vp, vp, sz, vp, vp, vp, vp, sz, vp, sz, vp, vp]
     L.gx_chain_info.argtypes = [vp, u64p, u64p, u64p, u64p, dp, dp]
+    u32 = ctypes.c_uint32
+    L.gx_revcomp.argtypes = [vp, sz, vp]
+    L.gx_revcomp_batch.argtypes = [vp, vp, vp, sz, u32, vp, sz, vp]
+    L.gx_suffix_index_search_strands.argtypes = [vp, vp, vp, sz, u32, vp, u32, vp, sz, vp]
+    L.gx_suffix_index_search_approx_strands.argtypes = [vp, vp, vp, sz, u32, u32, vp, u32, vp, vp, sz, vp]
+    L.gx_suffix_index_search_edit_strands.argtypes = [vp, vp, vp, sz, u32, u32, vp, u32, vp, vp, vp, sz, vp]
+    L.gx_suffix_index_match_stats_strands.argtypes = [vp, vp, vp, sz, u32, u32, vp]
+    L.gx_suffix_index_mems_strands.argtypes = [vp, vp, vp, sz, u32, u32, vp, sz, vp, vp]
+    L.gx_suffix_index_extend_strands.argtypes = [vp, vp, vp, sz, u32, vp, vp, vp, ctypes.POINTER(CScores), u32, vp, vp, sz,
+                                                 vp]
+    L.gx_strand_info.argtypes = [vp, u64p, u64p, dp]
     _lib = L
     return L
 
@@ -1119,6 +1134,62 @@ NO_DIST = 0xFFFFFFFF    # best_dist of a pattern without an occurrence
 ALL_HITS = 0xFFFFFFFF   # max_hits: every occurrence
 _FIRST_CAP = 1 << 22    # positions asked for before the count is known (GX_ECAP names the rest)
 _FIRST_RUNS = 8         # CIGAR runs a hit asked for before the count is known: a hit within three edits has at most seven
+STRANDS = {"forward": 1, "reverse": 2, "both": 3}   # GX_STRAND_FWD, GX_STRAND_REV, GX_STRAND_BOTH
+STRAND_PAD = 16         # GX_STRAND_PAD
+
+
+def _strands(strands) -> int:
+    """GX_STRAND_* of "forward", "reverse" or "both"; a number is handed to the library as it is."""
+    if isinstance(strands, str):
+        if strands not in STRANDS:
+            raise GxError(1, f"strands is {strands!r}, not 'forward', 'reverse' or 'both'")
+        return STRANDS[strands]
+    return int(strands)
+
+
+def _strand_items(result: dict, npat: int, s: int) -> dict:
+    """With anything but the forward strand alone: the caller's pattern and the strand (0 forward, 1 reverse)
+    of every item, beside the result's per-item arrays."""
+    if s != 1:
+        result["pattern"] = np.tile(np.arange(npat, dtype=np.uint32), 2 if s == 3 else 1)
+        result["strand"] = np.repeat(np.array([0, 1] if s == 3 else [1], np.uint8), npat)
+    return result
+
+
+def revcomp(b: bytes) -> bytes:
+    """gx_revcomp: the reverse complement of b over IUPAC in both cases; every other byte is its own complement."""
+    src = np.frombuffer(bytes(b), np.uint8)
+    dst = np.zeros(max(src.size, 1), np.uint8)
+    _check(lib().gx_revcomp(src.ctypes.data if src.size else None, src.size, dst.ctypes.data))
+    return dst[:src.size].tobytes()
+
+
+def revcomp_batch(patterns, strands="both", ctx: Optional["Context"] = None, pad: bool = False,
+                  cap: Optional[int] = None):
+    """gx_revcomp_batch: the item batch of `patterns` (as for SuffixIndex.search) on `strands`, exactly as the
+    stranded searches stage it: (packed uint8, offsets uint64 of items + 1).  With a context it is staged on the
+    device and copied back; ctx=None builds it on the host.  pad=True also returns the STRAND_PAD bytes staged
+    behind the items.  cap: the capacity handed to the call (None: what it needs)."""
+    s = _strands(strands)
+    packed, off, n = SuffixIndex._batch(patterns)
+    items = n * (2 if s == 3 else 1)
+    total = int(off[-1]) * (2 if s == 3 else 1)
+    want = total + (STRAND_PAD if pad else 0) if cap is None else cap
+    out = np.zeros(max(want, 1), np.uint8)
+    ooff = np.zeros(items + 1, np.uint64)
+    _check(lib().gx_revcomp_batch(ctx.ptr if ctx else None, packed.ctypes.data, off.ctypes.data, n, s, out.ctypes.data,
+                                  want, ooff.ctypes.data))
+    return out[:min(want, total + (STRAND_PAD if pad else 0))], ooff
+
+
+def strand_info(ctx: Optional["Context"] = None) -> dict:
+    """gx_strand_info of the last search-mode call on ctx: the items it staged, the reverse bytes the kernel
+    wrote and that kernel's device ms."""
+    ctx = ctx or default_context()
+    v = [ctypes.c_uint64() for _ in range(2)]
+    ms = ctypes.c_double()
+    _check(lib().gx_strand_info(ctx.ptr, ctypes.byref(v[0]), ctypes.byref(v[1]), ctypes.byref(ms)))
+    return {"items": v[0].value, "rc_bytes": v[1].value, "rc_ms": ms.value}
 
 
 class SuffixIndex:
@@ -1165,84 +1236,95 @@ class SuffixIndex:
         _check(rc)
         return out
 
-    def search(self, patterns, max_hits: int = 0) -> dict:
+    def search(self, patterns, max_hits: int = 0, strands="forward") -> dict:
         """gx_suffix_index_search for a batch: `patterns` is a sequence of bytes, or (packed, offsets) with
         pattern p = packed[offsets[p]:offsets[p + 1]].  Returns uint32 arrays "lo", "count", "prefix_len",
         "prefix_pos" (one entry per pattern) and, with max_hits > 0, "positions" (the first
         min(count, max_hits) suffix-array entries of each pattern's interval, ascending) and "hit_offsets"
-        (uint64, npat + 1).  max_hits = ALL_HITS reports every occurrence."""
-        packed, off, npat = self._batch(patterns)
+        (uint64, npat + 1).  max_hits = ALL_HITS reports every occurrence.
+        strands: "forward", "reverse" or "both" (gx_suffix_index_search_strands): every per-pattern array then
+        has one entry per item of the item batch (revcomp_batch), and "pattern" and "strand" (0 forward,
+        1 reverse) name each item's.  Positions are the forward text's."""
+        packed, off, ncall = self._batch(patterns)
+        sc = _strands(strands)
+        npat = ncall * (2 if sc == 3 else 1)   # the items
         hits = np.zeros(npat, HIT_DTYPE)
         out = None
         if max_hits <= 0:
-            _check(lib().gx_suffix_index_search(self.ptr, packed.ctypes.data, off.ctypes.data, npat, hits.ctypes.data,
-                                                0, None, 0, None))
+            _check(lib().gx_suffix_index_search_strands(self.ptr, packed.ctypes.data, off.ctypes.data, ncall, sc,
+                                                        hits.ctypes.data, 0, None, 0, None))
         else:
             hoff = np.zeros(npat + 1, np.uint64)
 
             def call(cap):
                 pos = np.zeros(cap, np.uint32)
-                return lib().gx_suffix_index_search(self.ptr, packed.ctypes.data, off.ctypes.data, npat, hits.ctypes.data,
-                                                    max_hits, pos.ctypes.data, cap, hoff.ctypes.data), pos
+                return lib().gx_suffix_index_search_strands(self.ptr, packed.ctypes.data, off.ctypes.data, ncall, sc,
+                                                            hits.ctypes.data, max_hits, pos.ctypes.data, cap,
+                                                            hoff.ctypes.data), pos
 
             pos = self._grown(npat, max_hits, hoff, call)
             out = {"positions": pos[:int(hoff[-1])], "hit_offsets": hoff}
         r = {k: np.ascontiguousarray(hits[k]) for k in ("lo", "count", "prefix_len", "prefix_pos")}
         if out:
             r.update(out)
-        return r
+        return _strand_items(r, ncall, sc)
 
-    def search_approx(self, patterns, k: int, max_hits: int = 0) -> dict:
+    def search_approx(self, patterns, k: int, max_hits: int = 0, strands="forward") -> dict:
         """gx_suffix_index_search_approx for a batch (`patterns` as for search): every start where a pattern
         matches with at most k substitutions (0 <= k <= APPROX_MAX_K, every pattern of k + 1 bytes or more).
         Returns uint32 arrays "count", "best_dist" (NO_DIST without an occurrence), "best_pos", "candidates"
         and, with max_hits > 0, "positions" (ascending per pattern), "distances" (uint8, beside them) and
-        "hit_offsets" (uint64, npat + 1).  max_hits = ALL_HITS reports every occurrence."""
-        packed, off, npat = self._batch(patterns)
+        "hit_offsets" (uint64, npat + 1).  max_hits = ALL_HITS reports every occurrence.  strands: as for search."""
+        packed, off, ncall = self._batch(patterns)
+        sc = _strands(strands)
+        npat = ncall * (2 if sc == 3 else 1)   # the items
         hits = np.zeros(npat, APPROX_HIT_DTYPE)
         out = None
         if max_hits <= 0:
-            _check(lib().gx_suffix_index_search_approx(self.ptr, packed.ctypes.data, off.ctypes.data, npat, k,
-                                                       hits.ctypes.data, 0, None, None, 0, None))
+            _check(lib().gx_suffix_index_search_approx_strands(self.ptr, packed.ctypes.data, off.ctypes.data, ncall, sc, k,
+                                                               hits.ctypes.data, 0, None, None, 0, None))
         else:
             hoff = np.zeros(npat + 1, np.uint64)
 
             def call(cap):
                 pos, dst = np.zeros(cap, np.uint32), np.zeros(cap, np.uint8)
-                return lib().gx_suffix_index_search_approx(self.ptr, packed.ctypes.data, off.ctypes.data, npat, k,
-                                                           hits.ctypes.data, max_hits, pos.ctypes.data, dst.ctypes.data,
-                                                           cap, hoff.ctypes.data), (pos, dst)
+                return lib().gx_suffix_index_search_approx_strands(self.ptr, packed.ctypes.data, off.ctypes.data, ncall, sc,
+                                                                   k, hits.ctypes.data, max_hits, pos.ctypes.data,
+                                                                   dst.ctypes.data, cap, hoff.ctypes.data), (pos, dst)
 
             pos, dst = self._grown(npat, max_hits, hoff, call)
             out = {"positions": pos[:int(hoff[-1])], "distances": dst[:int(hoff[-1])], "hit_offsets": hoff}
         r = {f: np.ascontiguousarray(hits[f]) for f in ("count", "best_dist", "best_pos", "candidates")}
         if out:
             r.update(out)
-        return r
+        return _strand_items(r, ncall, sc)
 
-    def search_edit(self, patterns, k: int, max_hits: int = 0, starts: bool = True) -> dict:
+    def search_edit(self, patterns, k: int, max_hits: int = 0, starts: bool = True, strands="forward") -> dict:
         """gx_suffix_index_search_edit for a batch (`patterns` as for search): every end e where a pattern
         matches a window s[b:e] with at most k substitutions, insertions and deletions (0 <= k <= APPROX_MAX_K,
         every pattern of k + 1 to EDIT_MAX_M bytes).  Returns uint32 arrays "count", "best_dist" (NO_DIST
         without an occurrence), "best_end", "candidates" and, with max_hits > 0, "ends" (each pattern's
         smallest ends, ascending), "distances" (uint8), "starts" (the shortest window's; None with
-        starts=False) and "hit_offsets" (uint64, npat + 1).  max_hits = ALL_HITS reports every occurrence."""
-        packed, off, npat = self._batch(patterns)
+        starts=False) and "hit_offsets" (uint64, npat + 1).  max_hits = ALL_HITS reports every occurrence.
+        strands: as for search; ends and starts are the forward text's."""
+        packed, off, ncall = self._batch(patterns)
+        sc = _strands(strands)
+        npat = ncall * (2 if sc == 3 else 1)   # the items
         hits = np.zeros(npat, EDIT_HIT_DTYPE)
         out = None
         if max_hits <= 0:
-            _check(lib().gx_suffix_index_search_edit(self.ptr, packed.ctypes.data, off.ctypes.data, npat, k,
-                                                     hits.ctypes.data, 0, None, None, None, 0, None))
+            _check(lib().gx_suffix_index_search_edit_strands(self.ptr, packed.ctypes.data, off.ctypes.data, ncall, sc, k,
+                                                             hits.ctypes.data, 0, None, None, None, 0, None))
         else:
             hoff = np.zeros(npat + 1, np.uint64)
 
             def call(cap):
                 end, dst = np.zeros(cap, np.uint32), np.zeros(cap, np.uint8)
                 sta = np.zeros(cap, np.uint32) if starts else None
-                return lib().gx_suffix_index_search_edit(self.ptr, packed.ctypes.data, off.ctypes.data, npat, k,
-                                                         hits.ctypes.data, max_hits, end.ctypes.data, dst.ctypes.data,
-                                                         sta.ctypes.data if starts else None, cap,
-                                                         hoff.ctypes.data), (end, dst, sta)
+                return lib().gx_suffix_index_search_edit_strands(self.ptr, packed.ctypes.data, off.ctypes.data, ncall, sc, k,
+                                                                 hits.ctypes.data, max_hits, end.ctypes.data,
+                                                                 dst.ctypes.data, sta.ctypes.data if starts else None, cap,
+                                                                 hoff.ctypes.data), (end, dst, sta)
 
             end, dst, sta = self._grown(npat, max_hits, hoff, call)
             tot = int(hoff[-1])
@@ -1251,35 +1333,46 @@ class SuffixIndex:
         r = {f: np.ascontiguousarray(hits[f]) for f in ("count", "best_dist", "best_end", "candidates")}
         if out:
             r.update(out)
-        return r
+        return _strand_items(r, ncall, sc)
 
-    def matching_stats(self, queries, max_len: int = 65535) -> dict:
+    def matching_stats(self, queries, max_len: int = 65535, strands="forward") -> dict:
         """gx_suffix_index_match_stats for a batch of long queries (`queries` as `patterns` of search, of any
         length): for every position of every query the longest prefix of its window (max_len bytes at most)
         that occurs in the text.  Returns uint32 arrays "len", "lo", "count", "pos" (one entry per query
-        position; query c's are at offsets[c]:offsets[c + 1]) and "offsets" (uint64, nq + 1)."""
+        position; query c's are at offsets[c]:offsets[c + 1]) and "offsets" (uint64, nq + 1).
+        strands: as for search; "offsets" are then the items', and a reverse item's positions are those of the
+        query's reverse complement (the same bases begin at m - position - len in the query)."""
         packed, off, nq = self._batch(queries)
-        st = np.zeros(int(off[-1]), MATCH_STAT_DTYPE)
-        _check(lib().gx_suffix_index_match_stats(self.ptr, packed.ctypes.data, off.ctypes.data, nq, max_len,
-                                                 st.ctypes.data if st.size else None))
+        sc = _strands(strands)
+        if sc == 3:
+            off_items = np.concatenate([off, off[-1] + off[1:]])
+        else:
+            off_items = off
+        st = np.zeros(int(off_items[-1]), MATCH_STAT_DTYPE)
+        _check(lib().gx_suffix_index_match_stats_strands(self.ptr, packed.ctypes.data, off.ctypes.data, nq, sc, max_len,
+                                                         st.ctypes.data if st.size else None))
         r = {f: np.ascontiguousarray(st[f]) for f in ("len", "lo", "count", "pos")}
-        r["offsets"] = off
-        return r
+        r["offsets"] = off_items
+        return _strand_items(r, nq, sc)
 
-    def mems(self, queries, min_len: int, max_mems: Optional[int] = None) -> dict:
+    def mems(self, queries, min_len: int, max_mems: Optional[int] = None, strands="forward") -> dict:
         """gx_suffix_index_mems for a batch of long queries: every maximal exact match of min_len bytes or
         more between a query and the text.  Returns uint32 arrays "qpos", "tpos", "length" (query c's MEMs at
         mem_offsets[c]:mem_offsets[c + 1], ordered by qpos, then tpos), "mem_offsets" (uint64, nq + 1) and
         "candidates" (uint64, the pairs examined per query).  max_mems=0 asks for the counts only (empty
         triples); None makes two calls, the counts first and then the exact capacity; a number is the
-        capacity of one call (GxError 7 when it is too small)."""
-        packed, off, nq = self._batch(queries)
+        capacity of one call (GxError 7 when it is too small).
+        strands: as for search; a reverse item's qpos is a position of the query's reverse complement (the same
+        bases begin at m - qpos - length in the query), tpos is the forward text's."""
+        packed, off, ncall = self._batch(queries)
+        sc = _strands(strands)
+        nq = ncall * (2 if sc == 3 else 1)   # the items
         moff, cand = np.zeros(nq + 1, np.uint64), np.zeros(nq, np.uint64)
 
         def call(mem, cap):
-            _check(lib().gx_suffix_index_mems(self.ptr, packed.ctypes.data, off.ctypes.data, nq, min_len,
-                                              mem.ctypes.data if mem is not None else None, cap, moff.ctypes.data,
-                                              cand.ctypes.data if nq else None))
+            _check(lib().gx_suffix_index_mems_strands(self.ptr, packed.ctypes.data, off.ctypes.data, ncall, sc, min_len,
+                                                      mem.ctypes.data if mem is not None else None, cap, moff.ctypes.data,
+                                                      cand.ctypes.data if nq else None))
 
         mem = np.zeros(0, MEM_DTYPE)
         if max_mems is None or max_mems <= 0:
@@ -1291,17 +1384,19 @@ class SuffixIndex:
             mem = np.zeros(max_mems, MEM_DTYPE)
             call(mem, max_mems)
             mem = mem[:int(moff[-1])]
-        return {"qpos": np.ascontiguousarray(mem["qpos"]), "tpos": np.ascontiguousarray(mem["tpos"]),
-                "length": np.ascontiguousarray(mem["len"]), "mem_offsets": moff, "candidates": cand}
+        return _strand_items({"qpos": np.ascontiguousarray(mem["qpos"]), "tpos": np.ascontiguousarray(mem["tpos"]),
+                              "length": np.ascontiguousarray(mem["len"]), "mem_offsets": moff, "candidates": cand},
+                             ncall, sc)
 
-    def chain_mems(self, queries, min_len: int, **params) -> dict:
+    def chain_mems(self, queries, min_len: int, strands="forward", **params) -> dict:
         """mems(queries, min_len), then chain_anchors on its result where the index lives (the device of a
-        device index, the host solver of a host index): {"mems": the one, "chains": the other}."""
-        m = self.mems(queries, min_len)
+        device index, the host solver of a host index): {"mems": the one, "chains": the other}.
+        strands: as for mems; every item's anchors are chained as they are, a reverse item being one more query."""
+        m = self.mems(queries, min_len, strands=strands)
         return {"mems": m, "chains": chain_anchors(m, ctx=self._ctx, host=self._ctx is None, **params)}
 
     def extend(self, reads, hits, scores: Optional["Scores"] = None, band: Optional[int] = None,
-               cigars: bool = True) -> dict:
+               cigars: bool = True, strands="forward") -> dict:
         """gx_suffix_index_extend: the reference's global alignment (alignment_table, then retrace) of every
         hit's window s[start:end] (s1) with its read (s2) on the cells |j - i| <= band.  `reads` as `patterns`
         of search; `hits` is a search_edit result or any mapping with "hit_offsets", "starts" and "ends"
@@ -1312,8 +1407,13 @@ class SuffixIndex:
         of hits would take longer to take apart than to align), "cigar_offsets" (uint64, hits + 1) and, with
         cigars, "cigar" (uint32
         runs len << 4 | op, M = 0, I = 1, D = 2, in read order; hit h's at cigar_offsets[h]:cigar_offsets[h + 1];
-        None with cigars=False)."""
-        packed, off, npat = self._batch(reads)
+        None with cigars=False).
+        strands: as for search; `hits` then has the hits of every item of the item batch (what search_edit
+        returns with the same strands), and a reverse item's hits are aligned against the read's reverse
+        complement, CIGAR in that order: what SAM reports for a reverse-strand read."""
+        packed, off, ncall = self._batch(reads)
+        sc_ = _strands(strands)
+        npat = ncall * (2 if sc_ == 3 else 1)   # the items
         hoff = np.ascontiguousarray(hits["hit_offsets"], np.uint64)
         sta = np.ascontiguousarray(hits["starts"], np.uint32)
         end = np.ascontiguousarray(hits["ends"], np.uint32)
@@ -1323,7 +1423,8 @@ class SuffixIndex:
         if sta.size < nh or end.size < nh:
             raise GxError(1, f"starts and ends have {sta.size} and {end.size} entries for {nh} hits")
         if band is None:
-            m = np.repeat(np.diff(off).astype(np.int64), np.diff(hoff).astype(np.int64)) if nh else np.zeros(0, np.int64)
+            lens = np.tile(np.diff(off).astype(np.int64), 2 if sc_ == 3 else 1)
+            m = np.repeat(lens, np.diff(hoff).astype(np.int64)) if nh else np.zeros(0, np.int64)
             band = int(np.abs(end[:nh].astype(np.int64) - sta[:nh].astype(np.int64) - m).max()) if nh else 0
         sc = (scores or Scores()).c()
         out = np.zeros(max(nh, 1), EXTEND_HIT_DTYPE)
@@ -1333,10 +1434,10 @@ class SuffixIndex:
         def call(cap):
             nonlocal cig
             cig = np.zeros(max(cap, 1), np.uint32) if cigars else None
-            return lib().gx_suffix_index_extend(self.ptr, packed.ctypes.data, off.ctypes.data, npat, hoff.ctypes.data,
-                                                sta.ctypes.data, end.ctypes.data, ctypes.byref(sc), band,
-                                                out.ctypes.data, cig.ctypes.data if cigars else None, cap,
-                                                coff.ctypes.data)
+            return lib().gx_suffix_index_extend_strands(self.ptr, packed.ctypes.data, off.ctypes.data, ncall, sc_,
+                                                        hoff.ctypes.data, sta.ctypes.data, end.ctypes.data,
+                                                        ctypes.byref(sc), band, out.ctypes.data,
+                                                        cig.ctypes.data if cigars else None, cap, coff.ctypes.data)
 
         rc = call(_FIRST_RUNS * nh)
         if rc == 7:
@@ -1345,14 +1446,14 @@ class SuffixIndex:
         r = {f: out[f][:nh] for f in EXTEND_HIT_DTYPE.names}
         r["cigar_offsets"] = coff
         r["cigar"] = cig[:int(coff[-1])] if cigars else None
-        return r
+        return _strand_items(r, ncall, sc_)
 
     def map_reads(self, reads, k: int, max_hits: int = 16, scores: Optional["Scores"] = None,
-                  band: Optional[int] = None) -> Tuple[dict, dict]:
+                  band: Optional[int] = None, strands="forward") -> Tuple[dict, dict]:
         """search_edit(reads, k, max_hits) with starts, then extend of what it reports (band=None: k).
-        Returns both results."""
-        found = self.search_edit(reads, k, max_hits, starts=True)
-        return found, self.extend(reads, found, scores, k if band is None else band)
+        Returns both results.  strands: handed to both calls (as for search)."""
+        found = self.search_edit(reads, k, max_hits, starts=True, strands=strands)
+        return found, self.extend(reads, found, scores, k if band is None else band, strands=strands)
 
     def sa(self) -> np.ndarray:
         """The suffix array, n + 1 entries (gx_suffix_index_export)."""

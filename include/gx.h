@@ -804,6 +804,85 @@ int  gx_chain_anchors(gx_context* ctx /* NULL: host */, const gx_mem* anchors, c
 int  gx_chain_info(const gx_context* ctx, uint64_t* anchors, uint64_t* segments, uint64_t* pair_evals, uint64_t* chains,
                    double* score_ms, double* chain_ms);
 
+/* ---------------------------------------------------------------------------
+ * Search mode on both strands.
+ *
+ * strand_comp, the complement table: an involution over all 256 bytes, IUPAC in
+ * both cases (A-T, C-G, R-Y, K-M, B-V, D-H; S, W, N and every other byte, U
+ * included, map to themselves), so a byte above '$' stays above it.
+ * rc(P)[j] = strand_comp(P[m - 1 - j]).
+ *
+ * The item batch of a caller's batch of n patterns P_0 .. P_{n-1} (T bytes):
+ *   GX_STRAND_FWD   the batch itself
+ *   GX_STRAND_REV   n items, item p = rc(P_p)
+ *   GX_STRAND_BOTH  2n items: item p = P_p, item n + p = rc(P_p), bytes back to
+ *                   back in that order (off'[p] = off[p], off'[n + p] = T + off[p])
+ *
+ * The contract of every _strands call: it returns, in every output array, every
+ * count and its return code, what the call without the suffix returns on the
+ * item batch of gx_revcomp_batch with the same remaining arguments, on the
+ * device and on a host index.  So
+ *   - every per-pattern array (hits, hit_offsets, candidates, mem_offsets, stats,
+ *     ...) has one entry per item: n for FWD and REV, 2n for BOTH; extend's
+ *     hit_offsets has items + 1 entries, and the hits of item n + p are aligned
+ *     against rc(P_p), which is what SAM reports for a reverse-strand read;
+ *   - positions, ends and starts are coordinates of the forward text;
+ *   - a reverse item's MEM qpos and the positions of match_stats are coordinates
+ *     of rc(Q): the same bases sit at m - qpos - len in the caller's query;
+ *   - a pattern equal to its own reverse complement reports in both items,
+ *     nothing is merged;
+ *   - GX_APPROX_CAND_BUDGET and the extend trace budget apply to the item batch.
+ * On a context the caller's bytes are copied to the device once, as without
+ * strands, and a kernel writes the reverse items behind them.
+ *
+ * Refusals, in this order: GX_EINVAL when strands is not 1, 2 or 3; what the
+ * call without the suffix refuses of the caller's batch, codes, texts and order
+ * unchanged, pattern numbers the caller's; then everything as the call without
+ * the suffix on the item batch: where a text names a pattern it is the item
+ * number.  One refusal is new: GX_ERANGE "strands: ..." when the item batch (the
+ * doubled bytes and items) fails the 32-bit conditions of the batch.  It stands
+ * directly behind the caller's batch's own 32-bit refusal, ahead of a NULL byte
+ * pointer and of a byte that is not above '$': like that refusal it is decided
+ * from the offsets, before a byte is read.  The calls without the suffix are the
+ * FWD case of these. */
+#define GX_STRAND_FWD 1u
+#define GX_STRAND_REV 2u
+#define GX_STRAND_BOTH 3u
+#define GX_STRAND_PAD 16   /* zero bytes staged behind an item batch */
+/* dst[j] = strand_comp(src[n - 1 - j]); src and dst do not overlap. */
+int  gx_revcomp(const uint8_t* src, size_t n, uint8_t* dst);
+/* The item batch exactly as the _strands calls stage it; with a context it is
+ * staged on the device (one copy in, the kernel, one copy out).  out_offsets is
+ * written first and in full; out_bytes may be NULL (offsets only).  GX_ECAP when
+ * the item bytes exceed out_cap: out_bytes untouched.  When out_cap has room for
+ * GX_STRAND_PAD bytes more, the zero bytes staged behind the items are written
+ * too.  Bytes are refused as the searches refuse them (above '$'). */
+int  gx_revcomp_batch(gx_context* ctx /* NULL: host */, const uint8_t* bytes, const uint64_t* offsets /* n+1 */, size_t n,
+                      uint32_t strands, uint8_t* out_bytes, size_t out_cap, uint64_t* out_offsets /* items+1 */);
+int  gx_suffix_index_search_strands(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets /* npat+1 */,
+                                    size_t npat, uint32_t strands, gx_search_hit* hits /* items */, uint32_t max_hits,
+                                    uint32_t* positions, size_t positions_cap, uint64_t* hit_offsets /* items+1 */);
+int  gx_suffix_index_search_approx_strands(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets,
+                                           size_t npat, uint32_t strands, uint32_t k, gx_approx_hit* hits, uint32_t max_hits,
+                                           uint32_t* positions, uint8_t* distances, size_t positions_cap,
+                                           uint64_t* hit_offsets);
+int  gx_suffix_index_search_edit_strands(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets, size_t npat,
+                                         uint32_t strands, uint32_t k, gx_edit_hit* hits, uint32_t max_hits, uint32_t* ends,
+                                         uint8_t* distances, uint32_t* starts, size_t positions_cap, uint64_t* hit_offsets);
+int  gx_suffix_index_extend_strands(gx_suffix_index* idx, const uint8_t* patterns, const uint64_t* offsets, size_t npat,
+                                    uint32_t strands, const uint64_t* hit_offsets /* items+1 */, const uint32_t* starts,
+                                    const uint32_t* ends, const gx_scores* scores, uint32_t band, gx_extend_hit* out,
+                                    uint32_t* cigar, size_t cigar_cap, uint64_t* cigar_offsets);
+int  gx_suffix_index_match_stats_strands(gx_suffix_index* idx, const uint8_t* queries, const uint64_t* offsets, size_t nq,
+                                         uint32_t strands, uint32_t max_len, gx_match_stat* stats /* item bytes */);
+int  gx_suffix_index_mems_strands(gx_suffix_index* idx, const uint8_t* queries, const uint64_t* offsets, size_t nq,
+                                  uint32_t strands, uint32_t min_len, gx_mem* mems, size_t mems_cap,
+                                  uint64_t* mem_offsets /* items+1 */, uint64_t* candidates /* items */);
+/* The last search-mode call on ctx: the items it staged, the reverse bytes the
+ * kernel wrote (0: forward only) and that kernel's device time (ms).
+ * Measurement and tests. */
+int  gx_strand_info(const gx_context* ctx, uint64_t* items, uint64_t* rc_bytes, double* rc_ms);
+
 #ifdef __cplusplus
 }
 #endif
